@@ -7,6 +7,11 @@ resample + WEIGHTED coadd) followed by configs[2] (one science frame subtracted
 against that coadd) once the subtraction kernels are built in.  Pixel accounting
 (SURVEY.md section 8(d)): Mpix = (frames resampled + frames subtracted) x 9.437184.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value,
+unit, ms_per_step, ...; `--dump-outputs DIR` also writes what the last timed step computed).
+Everything else it can measure - per-leg and per-kernel times, rooflines, the pipelined, nightly,
+CLIPPED and data-movement legs, the CPU baseline - runs with `--full` only.
+
 N > 1: one rank per GPU over RCCL, weak scaling - every rank resamples its own 32 frames
 of a 32 N deep stack, the partial sums are reduced across ranks, every rank then subtracts
 its own frame.  Either the driver starts the ranks (torch.distributed.run: RANK / LOCAL_RANK /
@@ -44,6 +49,8 @@ MFMA_F64_PEAK_TFLOPS = 78.6
 RESAMPLE_BYTES_PER_OUTPX = 16  # img+var read, img+var write
 MASK_BYTES_PER_OUTPX = 8       # + 4 B in / 4 B out when int32 masks ride along
 PMC_PROFILES = ['r06_pmc.json', 'r05_pmc.json']     # newest first; each stamped with the hash of the kernel sources it measured
+DUMP_SAMPLE = 1 << 19          # --dump-outputs: pixels written per plane (a fixed, seeded sample of larger planes)
+DUMP_SEED = 20240611
 
 
 def parse():
@@ -83,6 +90,14 @@ def parse():
                          'the reference a multi-rank run is compared with')
     ap.add_argument('--cpu-frames', type=int, default=2,
                     help='full-size frames the CPU baseline resamples and coadds')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: per-leg and per-kernel times, the rooflines, the pipelined, '
+                         'nightly, CLIPPED and data-movement legs, the per-rank exchange clocks and the CPU baseline '
+                         '(each still switched off by its --no-* flag).  Without it a run sets up, warms up, times '
+                         '--steps steps and prints the headline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64): '
+                         f'the same seeded sample of {DUMP_SAMPLE} pixels of every plane, and the fit summary')
     return ap.parse_args()
 
 
@@ -162,6 +177,31 @@ def pmc_traffic(pmc, section, prefixes):
     hits = [v for k, v in ks.items() if any(k.startswith(p) for p in prefixes) and v.get('hbm_bytes_per_launch') is not None]
     # (per launch of each kernel x its launches per coadd: the pre-pass kernels run once per stack like the fused one)
     return int(sum(v['hbm_bytes_per_launch'] * v.get('launches_per_coadd', 1) for v in hits)) if hits else None
+
+
+def dump_outputs(d, torch, planes, summary=None):
+    """--dump-outputs: ``planes`` (name -> device tensor) as d/<name>.npy - float planes in float32, integer (mask)
+    planes in float64, which holds them exactly.  A plane of more than DUMP_SAMPLE pixels is written as the pixels at
+    one sorted, seeded sample of flat indices (the same in every run; they are written too, as sample_index.npy), so
+    that what two builds computed can be compared output for output in a few tens of MB.  ``summary``: a ctypes
+    structure of numbers (the fit summary), written as one float64 vector."""
+    os.makedirs(d, exist_ok=True)
+    n = {t.numel() for t in planes.values()}
+    assert len(n) == 1, 'the planes of one step share one grid size'
+    n = n.pop()
+    pick = None
+    if n > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(d, 'sample_index.npy'), pick.astype(np.float64))
+    for name, t in planes.items():
+        flat = t.reshape(-1)
+        if pick is not None:
+            flat = flat.index_select(0, torch.from_numpy(pick).to(flat.device))
+        a = flat.cpu().numpy()
+        np.save(os.path.join(d, name + '.npy'), a.astype(np.float32 if a.dtype.kind == 'f' else np.float64))
+    if summary is not None:
+        np.save(os.path.join(d, 'subtract_summary.npy'),
+                np.array([float(getattr(summary, k)) for k, _ in summary._fields_], dtype=np.float64))
 
 
 
@@ -648,33 +688,43 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    # Timed region: only the roofline kernel carries HIP-event timers (two event records per
-    # launch cost dispatch latency: 0.7 ms per step with every scope timed).  The per-kernel
-    # table comes from one more, untimed-for-throughput step with every scope timed.
+    # Timed region: with --full only the roofline kernel carries HIP-event timers (two event records per
+    # launch cost dispatch latency: 0.7 ms per step with every scope timed); a plain run times no scope.
+    # The per-kernel table (--full) comes from one more, untimed-for-throughput step with every scope timed.
     # WEIGHTED / AVERAGE stacks run the fused kernel (frames looped inside the output tile);
     # CLIPPED / MEDIAN materialise the stack through the same kernel in STACK mode (ZM_COADD_FUSED=0:
     # k_resample frame by frame)
     fused = os.environ.get('ZM_COADD_FUSED', '1') != '0'
     roof_scope = 'coadd_fused' if fused else 'resample'
-    eng.timing(True, only=roof_scope)
-    eng.timing_reset()
+    if args.full:
+        eng.timing(True, only=roof_scope)
+        eng.timing_reset()
     dt = timed(step, args.steps)
     my_ms_per_step = 1e3 * local_dt['last'] / args.steps
-    eng.timing(False)
-    rs_ms, rs_cnt = eng.timing_read(roof_scope)
-    eng.timing_reset()
-    eng.timing(True)
-    step()
-    sync()
-    eng.timing(False)
-    names = ['coadd_fused', 'ff_headers', 'resample', 'mask_box', 'resample_mask', 'median_mad', 'prep', 'mesh_stats', 'mesh_filter',
-             'bk_expand', 'bk_rows', 'combine', 'lattice', 'hp_masks', 'hp_cells', 'hp_vectors', 'hp_gram',
-             'hp_solve', 'hp_chol', 'hp_apply']
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step handed its caller (timed() ends on sync(): its subtraction's summary is read)
+        planes = {'coadd_img': coadd.img, 'coadd_wgt': coadd.wgt, 'coadd_rms': ref_rms}
+        if coadd.mask is not None:
+            planes['coadd_mask'] = coadd.mask
+        if not args.no_subtract:
+            planes.update(sub_diff=sub.diff, sub_noise=sub.noise, sub_mask=sub.submask)
+        dump_outputs(args.dump_outputs, torch, planes, None if args.no_subtract else sub.info)
     kt = {}
-    for nme in names:
-        ms, cnt = eng.timing_read(nme)
-        if cnt:
-            kt[nme] = {'ms_per_step': ms, 'launches_per_step': cnt, 'avg_us': 1e3 * ms / cnt}
+    if args.full:
+        eng.timing(False)
+        rs_ms, rs_cnt = eng.timing_read(roof_scope)
+        eng.timing_reset()
+        eng.timing(True)
+        step()
+        sync()
+        eng.timing(False)
+        names = ['coadd_fused', 'ff_headers', 'resample', 'mask_box', 'resample_mask', 'median_mad', 'prep', 'mesh_stats', 'mesh_filter',
+                 'bk_expand', 'bk_rows', 'combine', 'lattice', 'hp_masks', 'hp_cells', 'hp_vectors', 'hp_gram',
+                 'hp_solve', 'hp_chol', 'hp_apply']
+        for nme in names:
+            ms, cnt = eng.timing_read(nme)
+            if cnt:
+                kt[nme] = {'ms_per_step': ms, 'launches_per_step': cnt, 'avg_us': 1e3 * ms / cnt}
     if sub.info.status != 0 and not args.no_subtract:
         print(f'rank {rank}: subtraction status {sub.info.status}', file=sys.stderr)
         sys.exit(3)
@@ -683,20 +733,21 @@ def main():
     mpix_per_step = frames_per_step * args.size * args.size / 1e6
     value = mpix_per_step * args.steps / dt
 
-    # per-leg rates (same objects, same inputs; each leg bracketed by its own sync)
+    # per-leg rates (--full; same objects, same inputs; each leg bracketed by its own sync)
     legs = {}
-    dt_c = timed(lambda: coadd_leg(coadd, dframes), args.steps)
-    legs['coadd_ms'] = 1e3 * dt_c / args.steps
-    legs['coadd_mpix_s'] = args.frames * world * npx / 1e6 * args.steps / dt_c
-    if not args.no_subtract:
-        dt_s = timed(lambda: sub_leg(coadd, sci), args.steps)
-        legs['subtract_ms'] = 1e3 * dt_s / args.steps
-        legs['subtract_mpix_s'] = world * npx / 1e6 * args.steps / dt_s
+    if args.full:
+        dt_c = timed(lambda: coadd_leg(coadd, dframes), args.steps)
+        legs['coadd_ms'] = 1e3 * dt_c / args.steps
+        legs['coadd_mpix_s'] = args.frames * world * npx / 1e6 * args.steps / dt_c
+        if not args.no_subtract:
+            dt_s = timed(lambda: sub_leg(coadd, sci), args.steps)
+            legs['subtract_ms'] = 1e3 * dt_s / args.steps
+            legs['subtract_mpix_s'] = world * npx / 1e6 * args.steps / dt_s
 
     # who ran where: the world RCCL / gloo actually formed
     me = {'rank': rank, 'device': local, 'name': torch.cuda.get_device_name(local), 'pid': os.getpid(),
           'ms_per_step': my_ms_per_step}
-    if multi:
+    if multi and args.full:
         # one more step with the exchange steps of this rank on a wall clock of their own (parallel.PROBE: each
         # bracketed by device synchronisations - never inside the timed region): what a first run on a real
         # multi-GPU node needs to explain its scaling
@@ -721,7 +772,7 @@ def main():
     # engines, each with two streams, all mapped onto GPU_MAX_HW_QUEUES hardware queues - the copy stream created here
     # shared a queue with a compute stream and the H2D copies of step k + 1 queued behind the kernels of step k:
     # with_pcie_ms 56 -> 69 ms in the round-4 line, 1.00 x the copy alone again when measured on a fresh process.)
-    order = os.environ.get('ZM_BENCH_ORDER', 'pipelined,clocks').split(',')
+    order = os.environ.get('ZM_BENCH_ORDER', 'pipelined,clocks').split(',') if args.full else []
     for leg in order:
         if leg == 'clocks' and world == 1 and rank == 0 and not args.no_clocks:
             clocks, tools = data_movement_clocks(args, z, dev, eng, torch, base, frames, sci, coadd, sub,
@@ -729,9 +780,9 @@ def main():
         if leg == 'pipelined' and world == 1 and rank == 0 and not args.no_subtract and not args.no_pipelined and sum_type:
             pipelined = pipelined_leg(args, z, dev, torch, base, dframes, sci, coadd, eng, no_ref_mask, npx, local, main_sub=sub)
     nightly = None
-    if world == 1 and rank == 0 and not args.no_subtract and not args.no_nightly:
+    if args.full and world == 1 and rank == 0 and not args.no_subtract and not args.no_nightly:
         nightly = nightly_leg(args, z, torch, base, frames, coadd, ref_rms, no_ref_mask, npx, local)
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         if sum_type and not args.no_secondary:
             secondary = secondary_clipped(args, z, dev, eng, base, dframes, local, timed, npx,
                                           full_step=None if args.no_subtract else (coadd_leg, sub_leg, sci), stream=coadd.stream)
@@ -739,7 +790,7 @@ def main():
     if rank == 0 and args.dump_coadd:
         torch.cuda.synchronize(device)
         np.save(args.dump_coadd, torch.stack([coadd.img, coadd.wgt]).cpu().numpy())
-    if rank == 0:
+    if rank == 0 and args.full:
         dom = max((k for k in kt if k != 'hp_chol'), key=lambda k: kt[k]['ms_per_step']) if kt else None   # (hp_chol lies inside hp_solve)
         if rs_cnt:      # the roofline kernel: from the timed region itself
             kt[roof_scope] = {'ms_per_step': rs_ms / args.steps, 'launches_per_step': rs_cnt // args.steps,
@@ -853,6 +904,7 @@ def main():
                           'valu_peak_TFLOPs': VALU_F32_PEAK_TFLOPS,
                           'what': 'template and template variance convolved with the spatially varying kernel, '
                                   '(2r+1)^2 taps each; bound by fp32 vector issue, not HBM (SURVEY 8(d))'}
+    if rank == 0:
         out = {
             'metric': 'Mpix/s resample->coadd->subtract, 3072x3072 frames',
             'value': value, 'unit': 'Mpix/s', 'n_gpus': world, 'steps': args.steps,
@@ -874,12 +926,15 @@ def main():
             'world': {'backend': backend if multi else None, 'native_rccl': os.environ.get('ZM_NATIVE_RCCL') == '1', 'world_size': world,
                       'launcher': os.environ.get('ZM_BENCH_LAUNCHER', 'external' if world > 1 else 'none'),
                       'ranks': ranks},
-            'legs': legs,
-            'solve_roofline': solve_roof,
-            'apply_roofline': apply_roof,
-            'kernels': kt,      # one extra step with every scope timed ('resample': the timed region)
-            'roofline': roofline,
         }
+        if args.full:
+            out.update({
+                'legs': legs,
+                'solve_roofline': solve_roof,
+                'apply_roofline': apply_roof,
+                'kernels': kt,      # one extra step with every scope timed ('resample': the timed region)
+                'roofline': roofline,
+            })
         if nightly is not None:
             out['nightly'] = nightly
         if pipelined is not None:
@@ -890,7 +945,7 @@ def main():
             out['clocks'] = clocks
         if tools is not None:
             out['reference_tools'] = tools
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(synth, args.size, args.combine, args.cpu_frames, args.frames)
         print(json.dumps(out))
     if multi:

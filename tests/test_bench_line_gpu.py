@@ -1,11 +1,13 @@
 """The one JSON line of bench.py (the driver's contract): every key the contract names, the roofline and
-cpu_baseline objects with their fields, the bookkeeping consistent (value = Mpix of the steps / time).
+cpu_baseline objects of a --full run with their fields, the bookkeeping consistent (value = Mpix of the steps / time);
+a plain run's line and its --dump-outputs.
 Run at a reduced size so that it takes seconds - the numbers are not looked at, the shape of the line is."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '2048', '--frames', '4', '--steps', '2', '--warmup', '1',
-           '--no-clocks', '--no-nightly', '--no-pipelined', '--cpu-frames', '1']
+           '--full', '--no-clocks', '--no-nightly', '--no-pipelined', '--cpu-frames', '1']
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -58,7 +60,7 @@ def test_bench_line_nightly_leg_with_batched_pools():
     (lanes x batch: the kernel fits of a batch as one chain of launches), no failed job, `batched_best` against one
     worker.  Reduced size; the numbers are not looked at."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '2048', '--frames', '4', '--steps', '2', '--warmup', '1',
-           '--no-clocks', '--no-pipelined', '--no-secondary', '--no-cpu-baseline', '--nightly-jobs', '4',
+           '--full', '--no-clocks', '--no-pipelined', '--no-secondary', '--no-cpu-baseline', '--nightly-jobs', '4',
            '--nightly-pools', '1,2', '--nightly-batches', '1x2,2x2,1x4']
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -82,7 +84,7 @@ def test_h2d_copies_overlap_the_step():
     1.22 unnoticed).  Sixteen full-size frames: the copy (1.6 GB, ~30 ms) is several times the device time, and the
     D2H of the products (0.23 GB on the same link: PCIe is full duplex, but the two directions are not free of each
     other - about 2 ms per step) stays below the tolerance."""
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--frames', '16', '--steps', '2', '--warmup', '1',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--frames', '16', '--steps', '2', '--warmup', '1', '--full',
            '--no-secondary', '--no-pipelined', '--no-nightly', '--no-cpu-baseline']
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900,
                          env=dict(os.environ, ZM_BENCH_PCIE_ONLY='1'))
@@ -93,3 +95,38 @@ def test_h2d_copies_overlap_the_step():
     p = c['pcie']
     assert p['h2d_copy_alone_ms'] > 2 * c['device_ms']            # (the case the overlap is for)
     assert p['ratio_to_max_of_copy_and_device'] <= 1.10, c
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline and nothing measured beside it; `--dump-outputs DIR` writes what
+    the last timed step computed (a seeded sample of each plane, float32 / float64, well under 64 MB), and a second
+    process with the same arguments writes the same numbers."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '2048', '--frames', '4', '--steps', '3',
+               '--warmup', '1', '--dump-outputs', str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in line, k
+        assert line['steps'] == 3 and line['unit'] == 'Mpix/s' and line['dtype'] == 'f32' and line['higher_is_better'] is True
+        assert line['value'] == pytest.approx((4 + 1) * 2048 * 2048 / 1e6 / (line['ms_per_step'] * 1e-3), rel=1e-6)
+        for k in ('legs', 'kernels', 'roofline', 'solve_roofline', 'cpu_baseline', 'clipped', 'nightly', 'pipelined', 'clocks'):
+            assert k not in line, k
+        files = sorted(p.name for p in d.iterdir())
+        assert files == sorted(f'{n}.npy' for n in ('coadd_img', 'coadd_wgt', 'coadd_rms', 'coadd_mask', 'sub_diff',
+                                                     'sub_noise', 'sub_mask', 'sample_index', 'subtract_summary'))
+        assert sum(p.stat().st_size for p in d.iterdir()) < 64e6
+        a = {p.stem: np.load(p) for p in d.iterdir()}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        idx = a['sample_index']
+        assert idx.shape == a['coadd_img'].shape and np.all(np.diff(idx) > 0) and idx[-1] < 2048 * 2048
+        assert (a['coadd_wgt'] > 0).mean() > 0.9 and np.isfinite(a['coadd_img']).all()
+        assert np.isfinite(a['sub_diff']).mean() > 0.9 and a['subtract_summary'].shape == (10,)
+        dumps.append(a)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)

@@ -27,7 +27,7 @@ HAVE_HIPCC = shutil.which('hipcc') is not None or os.path.exists('/opt/rocm/bin/
 def built_asm(src, tmp_path):
     """The device assembly of a translation unit: the file the build kept next to the object when it is at least as
     new as the source (the instructions that are in libzudsmi.so), else a compile with the build's own flags."""
-    objdir = build.LIBDIR / 'obj'
+    objdir = build.OBJDIR
     asm = build.device_asm(objdir, src)
     path = os.path.join(CSRC, src)
     if asm.exists() and asm.stat().st_mtime >= os.path.getmtime(path):

@@ -12,7 +12,7 @@ done
 for r in $(seq $reps); do
     for v in $names; do
         cp tools/_build/lib_$v.so zuds-pipeline_amd/lib/libzudsmi.so || exit 1
-        timeout -k 10 500 python3 bench.py --steps 5 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-pipelined 2>/dev/null | python3 -c "
+        timeout -k 10 500 python3 bench.py --full --steps 5 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-pipelined 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); n = d['nightly']
 print('== $v (pass $r)', {k: round(v['ms_per_subtraction'], 2) for k, v in n['pools'].items()}, {k: round(v['ms_per_subtraction'], 2) for k, v in n['batched'].items()}, 'best', round(n['batched_best']['ms_per_subtraction'], 3))"

@@ -3,7 +3,7 @@ import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, 'bench.py', '--no-cpu-baseline'] + sys.argv[1:],
+out = subprocess.run([sys.executable, 'bench.py', '--full', '--no-cpu-baseline'] + sys.argv[1:],
                      capture_output=True, text=True)
 lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
 if not lines:

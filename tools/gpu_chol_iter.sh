@@ -12,7 +12,7 @@ tail -3 $out/tests.log
 timeout -k 10 600 python3 tools/fuzz_subtract.py $nf 707 > $out/fuzz.log 2>&1 || { tail -20 $out/fuzz.log; exit 1; }
 tail -2 $out/fuzz.log
 [ -x tools/_build/potrf_probe ] && timeout -k 10 120 tools/_build/potrf_probe | grep "^form\|differ"
-B="bench.py --steps 10 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-pipelined"
+B="bench.py --full --steps 10 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-pipelined"
 timeout -k 10 400 python3 $B > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 python3 -c "
 import json; d = json.loads([l for l in open('$out/bench.json') if l.startswith('{')][-1])

@@ -20,7 +20,7 @@ for pass in 1 2; do
 done
 echo "== own: ablations (1 no pixels, 2 no prep, 4 no staging loads)"
 ZM_FF_FORM=own timeout -k 10 300 python3 tools/ff_probe.py --dbg 0,1,2,4,6,7 2>&1 | grep ZM_FF_DBG || exit 1
-B="bench.py --steps 10 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
+B="bench.py --full --steps 10 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
 for form in dma own; do
     ZM_FF_FORM=$form ZM_FF_PROF=1 timeout -k 10 300 python3 $B --no-subtract --steps 2 > $out/prof_$form.json 2> $out/prof_$form.err
     echo "$form: $(grep phases $out/prof_$form.err | tail -1)"

@@ -21,7 +21,7 @@ for pass in 1 2 3; do
         echo "== own, deal $d prio $pr (pass $pass)  $(ZM_FF_DEAL=$d ZM_FF_PRIO=$pr timeout -k 10 200 python3 tools/ff_probe.py --dbg 0 2>&1 | grep ZM_FF_DBG | cut -c1-90)"
     done
 done
-B="bench.py --steps 10 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
+B="bench.py --full --steps 10 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
 for c in $profs; do
     d=${c%%:*}; pr=${c##*:}
     ZM_FF_DEAL=$d ZM_FF_PRIO=$pr ZM_FF_PROF=2 timeout -k 10 300 python3 $B --no-subtract --steps 2 > $out/prof_own_${d}_${pr}.json 2> $out/prof_own_${d}_$pr.err

@@ -9,7 +9,7 @@ tag=${1:-round}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="bench.py --steps 20 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
+B="bench.py --full --steps 20 --warmup 2 --no-clocks --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
 if [ "${2:-tests}" = tests ]; then
     timeout -k 10 1000 python3 -m pytest tests -m gpu -x -q > $out/tests.log 2>&1 || { tail -30 $out/tests.log; exit 1; }
     tail -2 $out/tests.log
@@ -40,7 +40,7 @@ python3 tools/make_pmc_json.py $out $out/pmc.json
 cp $out/pmc.json profiles/r06_pmc.json
 cp $out/bench.json $out/bench_short.json
 rm -rf $out/pmc_*_FETCH_SIZE $out/pmc_*_WRITE_SIZE $out/pmc_*_SQ $out/prof    # (raw traces: tens of MB)
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 python3 -c "
 import json; d = json.loads([l for l in open('$out/bench.json') if l.startswith('{')][-1])
 print(d['value'], d['ms_per_step'], d['legs'])

@@ -45,7 +45,7 @@ def main(tag):
           f'hash to `kernel_sources_sha16` = `{pmc.get("kernel_sources_sha16")}` in `{tag}_pmc.json`{tests}).  This section is generated: '
           f'`python3 tools/make_profiles_readme.py {tag}`.\n')
     print('| File | What |\n|---|---|')
-    print(f'| `{tag}_bench.json` | the one-line output of `python bench.py --gpus 1 --steps 20 --warmup 5`: **{bench["value"]:.0f} Mpix/s, '
+    print(f'| `{tag}_bench.json` | the one-line output of `python bench.py --full --gpus 1 --steps 20 --warmup 5`: **{bench["value"]:.0f} Mpix/s, '
           f'{bench["ms_per_step"]:.2f} ms per step**; `roofline` ({r["kernel"]}: {r["frac"]:.3f} of 8 TB/s on what it reads and writes, '
           f'{r.get("frac_of_achievable", float("nan")):.3f} of the 6.29 TB/s a copy reaches, traffic {r.get("wasted") or float("nan"):.2f} x the '
           f'algorithmic bytes, `valu_busy_frac` {r.get("valu_busy_frac")}; the leg {(r.get("leg") or {}).get("leg_frac", float("nan")):.3f}; '
@@ -61,7 +61,7 @@ def main(tag):
           f'{(oa.get("device") or {}).get("reference_from_images_ms", float("nan")):.0f} / {(oa.get("device") or {}).get("subtraction_from_images_ms", float("nan")):.0f} ms, '
           f'cold {(oa.get("cold") or {}).get("reference_from_images_ms", float("nan")):.0f} / {(oa.get("cold") or {}).get("subtraction_from_images_ms", float("nan")):.0f} ms), '
           f'`cpu_baseline` ({(bench.get("cpu_baseline") or {}).get("value", float("nan")):.1f} Mpix/s on {(bench.get("cpu_baseline") or {}).get("cores")} threads) |')
-    print(f'| `{tag}_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats` of `bench.py --steps 20 --warmup 2 --no-clocks --no-cpu-baseline '
+    print(f'| `{tag}_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats` of `bench.py --full --steps 20 --warmup 2 --no-clocks --no-cpu-baseline '
           f'--no-secondary --no-nightly --no-pipelined` (calls, total, average, min, max, **median**): `{fn[:40]}` {fus:.0f} us average, '
           f'`{cn[:16]}` median {cus:.0f} us, `{an[:18]}` {aus:.0f} us, `{bn[:18]}` median {bus:.0f} us |')
     print(f'| `{tag}_pmc_summary.txt`, `{tag}_pmc_summary_clipped.txt` | per-kernel means of the separate `--pmc` passes (`FETCH_SIZE`, '

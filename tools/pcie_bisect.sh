@@ -5,7 +5,7 @@ set -o pipefail
 out=gpurun_out/${1:-pcie}
 mkdir -p $out
 export TMPDIR=/tmp ZM_BENCH_PCIE_ONLY=1
-B="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
+B="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-nightly --no-pipelined"
 run() {
     name=$1; shift
     env "$@" timeout -k 10 300 python3 $B > $out/$name.json 2> $out/$name.err || { tail -5 $out/$name.err; return; }

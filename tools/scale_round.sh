@@ -26,11 +26,11 @@ run() {   # run <name> <ranks> <env...> -- <bench args...>
     shift
     local port=$((29600 + RANDOM % 300))
     if [ "$n" = 1 ]; then
-        env "${envs[@]}" timeout -k 10 900 python3 bench.py --gpus 1 --steps $STEPS --warmup 3 --no-clocks --no-cpu-baseline --no-nightly --no-pipelined --no-secondary $ZM_SCALE_ARGS "$@" \
+        env "${envs[@]}" timeout -k 10 900 python3 bench.py --full --gpus 1 --steps $STEPS --warmup 3 --no-clocks --no-cpu-baseline --no-nightly --no-pipelined --no-secondary $ZM_SCALE_ARGS "$@" \
             > $out/$name.json 2> $out/$name.err
     else
         env "${envs[@]}" timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-            bench.py --gpus $n --steps $STEPS --warmup 3 --no-clocks --no-cpu-baseline --no-nightly --no-pipelined --no-secondary $ZM_SCALE_ARGS "$@" \
+            bench.py --full --gpus $n --steps $STEPS --warmup 3 --no-clocks --no-cpu-baseline --no-nightly --no-pipelined --no-secondary $ZM_SCALE_ARGS "$@" \
             > $out/$name.json 2> $out/$name.err
     fi
     local rc=$?

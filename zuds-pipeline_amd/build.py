@@ -13,12 +13,15 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / 'csrc'
 LIBDIR = HERE / 'lib'
 LIBNAME = 'libzudsmi.so'
+# objects and the assembly kept beside them: a git-ignored directory, so that a build changes no committed file
+# (lib/obj/ holds the assembly of an earlier build, committed with the sources; no build writes there)
+OBJDIR = LIBDIR / 'build'
 
 SOURCES = ['ctx.hip', 'wcs_host.hip', 'resample.hip', 'resample_opts.hip', 'maskbox.hip', 'fused_host.hip', 'fused_dma.hip', 'fused_own.hip', 'combine.hip',
            'background.hip', 'api_coadd.hip', 'hotpants.hip', 'hp_vectors.hip', 'hp_apply.hip', 'api_subtract.hip', 'select_bracket.hip', 'elementwise.hip', 'photometry.hip', 'fitsio.hip', 'detect.hip', 'comm.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
          '-Wno-unused-result']
-# the device assembly of every translation unit stays next to its object (obj/<stem>-hip-amdgcn-amd-amdhsa-gfx950.s):
+# the device assembly of every translation unit stays next to its object (build/<stem>-hip-amdgcn-amd-amdhsa-gfx950.s):
 # it IS what was assembled into the object, and isa_checks lints it before the library is linked
 TEMPS = ['-save-temps=obj']
 EXTRA_FLAGS = {}     # per-source additions, e.g. {'x.hip': ['-mllvm', '...']}
@@ -75,7 +78,7 @@ def lint_built(objdir, sources, verbose=True):
 def build(force=False, verbose=True):
     """Compile every HIP translation unit and link libzudsmi.so."""
     LIBDIR.mkdir(exist_ok=True)
-    objdir = LIBDIR / 'obj'
+    objdir = OBJDIR
     objdir.mkdir(exist_ok=True)
     hipcc = _hipcc()
     headers = list(CSRC.glob('*.h')) + [HERE.parent / 'include' / 'zudsmi.h']

@@ -15,6 +15,9 @@ iterated +-3 sigma clipping around the histogram median, mode = 2.5 med - 1.5
 mean when |mean - med| < 0.3 sigma else the median; bad meshes (< 50 % good
 pixels) filled from the nearest good ones; 3x3 median filter of the mesh maps;
 natural bicubic spline through mesh centres back to full resolution.
+
+A mesh sample is a pixel whose value p has ``|p| < BIG``, which excludes NaN, +-inf and values at or below
+-BIG, and whose weight (when there is a weight map) is above WEIGHT_THRESH.  The HIP kernels apply the same test.
 """
 import numpy as np
 
@@ -146,7 +149,7 @@ def mesh_maps(img, wgt=None, mesh=128):
             y0, y1 = j * mesh, min((j + 1) * mesh, ny)
             x0, x1 = i * mesh, min((i + 1) * mesh, nx)
             p = img[y0:y1, x0:x1].ravel()
-            ok = p > -BIG
+            ok = np.abs(p) < BIG            # a sample: not NaN, not +-inf, not <= -BIG (the bad-mesh marker)
             if wgt is not None:
                 ok &= (wgt[y0:y1, x0:x1].ravel() > WEIGHT_THRESH)
             p = p[ok]

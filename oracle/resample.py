@@ -20,9 +20,20 @@ Arithmetic (SWarp >= 2.38 ``interpolate.c`` as published; adopted conventions):
   kernel (every other tap is exactly 0) its centre pixel only, so that identity /
   integer-shift alignments keep their borders, as SWarp's edge-truncated kernels
   do - when any tap with non-zero weight lands on a bad input pixel
-  (weight <= WEIGHT_THRESH), or when the interpolated variance is <= 0;
+  (weight <= WEIGHT_THRESH, or a value that is NaN or +-inf), when the interpolated variance is <= 0, or when it
+  is >= BADVAR_TEST (below);
 * flux: ``out = interp * fscale``, variance ``* fscale**2`` where ``fscale`` =
   FLXSCALE x (A_out / A_in) (fixed pixel-area ratio).
+
+Non-finite values and the bad-tap rule (the convention the HIP kernels follow): an input pixel is bad when its
+weight is at or below WEIGHT_THRESH or when its value is not finite (NaN, +inf, -inf; ZTF frames carry NaN
+pixels, ``zuds/constants.py:59``), with or without a weight map and for every kernel, NEAREST included.  A bad
+input pixel takes part as value 0 and variance BIGVAR.  An output is bad when its interpolated variance, in the
+units of 1 / weight (var_scale / weight on the device; this function's callers fold var_scale into ``wgt``), is
+``>= BADVAR_TEST = 1e14``: that is how the kernels tell a BIGVAR tap from good ones under any non-zero tap, and
+there is no cheap exact alternative.  It also makes a good pixel whose weight lies between WEIGHT_THRESH and about
+1e-14 (a variance of 1e14 and more, in the same units) bad, where SWarp's ``WEIGHT_THRESH 1e-30`` alone would keep
+it; realistic ZTF weights (1e-4 to 1e-1) sit ten decades away from that edge.
 
 Integer masks go through the same footprint (``mask.swarp`` keeps
 ``RESAMPLING_TYPE LANCZOS3``): output mask = bitwise OR of every input mask
@@ -48,6 +59,7 @@ from .wcs import map_out_to_in
 LANCZOS3, BILINEAR, NEAREST = 3, 1, 0
 SNAP = 1e-5
 BIGVAR = 1e30
+BADVAR_TEST = 1e14      # an interpolated variance at or above this: a bad tap was hit (module docstring)
 WEIGHT_THRESH = 1e-30
 
 
@@ -133,7 +145,8 @@ def resample(img, wgt, px, py, kind=LANCZOS3, fscale=1.0, mask=None,
     px, py: 0-based input positions per output pixel.  Returns
     (out_img, out_wgt, out_mask_or_None), float64 / int64.  ``edge`` / ``mask_resample``: module docstring.
     ``debug``: a dict that receives 'mask_float', the interpolated mask before rounding (tests compare a device that
-    evaluates fp32 table taps with it: the integers agree except within rounding distance of a half).
+    evaluates fp32 table taps with it: the integers agree except within rounding distance of a half), and 'vacc', the
+    interpolated variance of every covered output without a bad tap (0 elsewhere; not for NEAREST).
     """
     img = np.asarray(img, dtype=np.float64)
     ny, nx = img.shape
@@ -141,8 +154,12 @@ def resample(img, wgt, px, py, kind=LANCZOS3, fscale=1.0, mask=None,
         var = np.ones_like(img)
     else:
         w = np.asarray(wgt, dtype=np.float64)
-        with np.errstate(divide='ignore'):
+        with np.errstate(divide='ignore', invalid='ignore'):
             var = np.where(w > WEIGHT_THRESH, 1.0 / np.where(w > 0, w, 1.0), BIGVAR)
+    # a non-finite value is a bad input pixel: value 0, variance BIGVAR
+    finite = np.isfinite(img)
+    img = np.where(finite, img, 0.0)
+    var = np.where(finite, var, BIGVAR)
     bad_in = var >= BIGVAR
     oshape = px.shape
     out = np.zeros(oshape)
@@ -154,9 +171,11 @@ def resample(img, wgt, px, py, kind=LANCZOS3, fscale=1.0, mask=None,
         ok = (ix >= 0) & (ix < nx) & (iy >= 0) & (iy < ny)
         ixc = np.clip(ix, 0, nx - 1)
         iyc = np.clip(iy, 0, ny - 1)
-        good = ok & ~bad_in[iyc, ixc]
+        v = var[iyc, ixc]
+        good = ok & ~bad_in[iyc, ixc] & (v > 0) & (v < BADVAR_TEST)
         out = np.where(good, img[iyc, ixc] * fscale, 0.0)
-        outw = np.where(good, 1.0 / (var[iyc, ixc] * fscale * fscale), 0.0)
+        with np.errstate(divide='ignore'):
+            outw = np.where(good, 1.0 / (v * fscale * fscale), 0.0)
         if mask is not None:
             outm = np.where(ok, mask[iyc, ixc], 0).astype(np.int64)
         return out, outw, outm
@@ -194,7 +213,9 @@ def resample(img, wgt, px, py, kind=LANCZOS3, fscale=1.0, mask=None,
                 if mask is not None:
                     macc |= np.where(nz, mask[yy, xx], 0)
                     mflt += wt * mask[yy, xx]            # (the mask as the image SWarp takes it for)
-        good = inb & ~anybad & (vacc > 0)
+        good = inb & ~anybad & (vacc > 0) & (vacc < BADVAR_TEST)
+        if debug is not None:
+            debug.setdefault('vacc', np.zeros(oshape))[sl] = np.where(inb & ~anybad, vacc, 0.0)
         if mask is not None and mask_resample == MASK_LANCZOS_ROUND:
             macc = np.rint(mflt).astype(np.int64)
             if debug is not None:

@@ -494,7 +494,7 @@ __global__ __launch_bounds__(BKF_THREADS, BKF_WPS) void k_mesh_stats_fast(const 
     if (SEL != 1) {
         const size_t i00 = (size_t)y0 * nx + x0;
         const float p0 = img[i00], w0 = wgt ? wgt[i00] : 1.f;
-        khint = (w0 > thr && p0 > -BK_BIG) ? p0 : qnan;
+        khint = (w0 > thr && fabsf(p0) < BK_BIG) ? p0 : qnan;
     }
     const int c4 = (tid & 31) * 4, r32 = tid >> 5;
 #pragma unroll
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(BKF_THREADS, BKF_WPS) void k_mesh_stats_fast(const 
             }
             if (SEL != 1) {
                 const float val = pv[j];
-                v[4 * k + j] = (good && (val > -BK_BIG)) ? val : qnan;
+                v[4 * k + j] = (good && (fabsf(val) < BK_BIG)) ? val : qnan;   // (no NaN, no +-inf: oracle/background.py)
             }
         }
     }
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(BKF_THREADS, BKF_WPS) void k_mesh_stats_fast(const 
     for (int k = 0; k < BKF_PX; ++k) {
         const float x = v[k];
         const float val = 1.0f / x;
-        const bool ok = (x == x) && (val > -BK_BIG) && (val == val);
+        const bool ok = (x == x) && (fabsf(val) < BK_BIG);     // the sample is 1 / weight: |1 / w| < BIG, as any sample
         v[k] = ok ? val : qnan;
     }
     __syncthreads();                                       // (the slots and the histogram of the first statistic are consumed)
@@ -701,7 +701,7 @@ __global__ __launch_bounds__(BK_THREADS) void k_mesh_stats(const float* __restri
             good = ww > wthresh;
             v = good ? 1.0f / ww : 0.f;
         }
-        good = good && (v > -BK_BIG) && (v == v);
+        good = good && (fabsf(v) < BK_BIG);
         *ok = good;
         return v;
     };

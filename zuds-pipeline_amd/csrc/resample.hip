@@ -337,7 +337,8 @@ __global__ __launch_bounds__(256, 4) void k_resample(
     // pair_scale != 0 (round 6, zm_align_pair_dev): the plane holds TWO images {a, b} that share the geometry - the
     // reference and its rms map on their way to a science grid (zuds/subtraction.py:109, zuds/hotpants.py:51: two
     // SWarp runs there, two launches here until now) - and both channels are values: b leaves scaled by pair_scale,
-    // nothing is a variance, validity is the footprint test alone.  Per channel the operations of a single alignment.
+    // nothing is a variance, validity is the footprint test plus, per channel, no non-finite value under a non-zero
+    // tap.  Per channel the operations of a single alignment.
     extern __shared__ float4 smem4[];
     rs_hdr* HR = reinterpret_cast<rs_hdr*>(smem4);                 // ring of 3 headers
     // Lanczos-3: the tap table sits between the headers and the pixel tile
@@ -544,9 +545,62 @@ __global__ __launch_bounds__(256, 4) void k_resample(
                         p += spitch;
                     }
                 }
-                if (pair_scale != 0.f) {
-                    res.x = acc * fscale;
-                    res.y = vacc * pair_scale;
+                if (MASKOP != 2 && pair_scale != 0.f) {     // (a pair never accumulates a mask: launch check)
+                    // A NaN or +-inf under the footprint leaves acc or vacc non-finite (it survives every multiply and
+                    // add of these sums), so a finite pair needs nothing more.  Otherwise the pixel is redone with every
+                    // non-finite input as 0 and a flag per channel, set when a non-zero tap lands on one: what
+                    // zm_resample_dev without weights does to that channel alone (a {0, BIGVAR} input pixel, an output
+                    // of 0), on both paths - the LDS path multiplies the zero taps of a delta axis too.
+                    bool bada = false, badb = false;
+                    if (!(__builtin_isfinite(acc) && __builtin_isfinite(vacc))) {
+                        if (use_lds) {
+                            const float2* p = tile + (iyr + OFF) * bw + (ixr + OFF);
+                            zm_v2f av = (zm_v2f){0.f, 0.f};
+#pragma unroll
+                            for (int r = 0; r < NT; ++r) {
+                                float2 s[NT];
+                                lds_row<NT>::read(p, s);
+                                zm_v2f rv2 = (zm_v2f){0.f, 0.f};
+#pragma unroll
+                                for (int c = 0; c < NT; ++c) {
+                                    const bool nz = tw[c].x != 0.f && tw[r].y != 0.f;
+                                    const bool fa = __builtin_isfinite(s[c].x), fb = __builtin_isfinite(s[c].y);
+                                    bada = bada || (nz && !fa);
+                                    badb = badb || (nz && !fb);
+                                    rv2 = __builtin_elementwise_fma((zm_v2f){tw[c].x, tw[c].x},
+                                                                    (zm_v2f){fa ? s[c].x : 0.f, fb ? s[c].y : 0.f}, rv2);
+                                }
+                                av = __builtin_elementwise_fma((zm_v2f){tw[r].y, tw[r].y}, rv2, av);
+                                p += bw;
+                            }
+                            acc = av.x;
+                            vacc = av.y;
+                        } else {
+                            const float2* p = src + (size_t)iy * spitch + ix;
+                            acc = 0.f;
+                            vacc = 0.f;
+                            for (int r = 0; r < NT; ++r) {
+                                float ra = 0.f, rv = 0.f;
+                                if (tw[r].y != 0.f) {
+                                    for (int c = 0; c < NT; ++c) {
+                                        if (tw[c].x != 0.f) {
+                                            const float2 s = p[c];
+                                            const bool fa = __builtin_isfinite(s.x), fb = __builtin_isfinite(s.y);
+                                            bada = bada || !fa;
+                                            badb = badb || !fb;
+                                            ra = fmaf(tw[c].x, fa ? s.x : 0.f, ra);
+                                            rv = fmaf(tw[c].x, fb ? s.y : 0.f, rv);
+                                        }
+                                    }
+                                }
+                                acc = fmaf(tw[r].y, ra, acc);
+                                vacc = fmaf(tw[r].y, rv, vacc);
+                                p += spitch;
+                            }
+                        }
+                    }
+                    res.x = bada ? 0.f : acc * fscale;
+                    res.y = badb ? 0.f : vacc * pair_scale;
                 } else if (vacc > 0.f && vacc < ZM_BADVAR_TEST) {
                     res.x = acc * fscale;
                     res.y = __builtin_amdgcn_rcpf(vacc * fscale2);      // 1 ulp: one instruction
@@ -666,8 +720,8 @@ int zm_launch_resample(zm_ctx* ctx, const float2* src, int nx, int ny, int spitc
                        float2* dst, int onx, int ony, int lds_elems, const int32_t* mask,
                        int32_t* macc, int mop, int mkind, int mfirst, float* plane_a, float* plane_b, float pair_scale) {
     dim3 blk(256, 1, 1), grd(zm_div_up(onx, TW), zm_div_up(ony, TH), 1);
-    ZM_CHECK(pair_scale == 0.f || (kernel != ZM_RESAMPLE_NEAREST && plane_a && plane_b && ctx->edge == ZM_EDGE_ZERO),
-             "zm_launch_resample: a pair of images takes LANCZOS3 / BILINEAR, two output planes and the default edge rule");
+    ZM_CHECK(pair_scale == 0.f || (kernel != ZM_RESAMPLE_NEAREST && plane_a && plane_b && ctx->edge == ZM_EDGE_ZERO && mop != 2),
+             "zm_launch_resample: a pair of images takes LANCZOS3 / BILINEAR, two output planes, the default edge rule and no mask accumulation");
     dim3 rgrd(zm_div_up(onx, TW), zm_div_up(ony, RTH), 1);     // k_resample: 64 x 32 tiles
     if (!mask || !macc) mop = 0;
     if (lds_elems > RS_PFCAP) lds_elems = RS_PFCAP;      // what the prefetch registers can stage

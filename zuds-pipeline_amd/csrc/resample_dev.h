@@ -101,12 +101,12 @@ __device__ inline void bk_eval4(const float* __restrict__ bk, int nbx, int nby, 
 }
 
 // One prepped pixel {value, variance}: background off, variance = var_scale / weight (a weight at
-// or below the threshold, a NaN pixel: bad = {., BIGVAR}).  The quotient is a reciprocal estimate
-// and a multiply (1 ulp; the parity tolerance of a resampled weight is 5e-5): the staging of the
-// fused coadd evaluates this once per staged pixel.
+// or below the threshold: bad = {., BIGVAR}; a NaN or +-inf value: bad = {0, BIGVAR}, oracle/resample.py).
+// The quotient is a reciprocal estimate and a multiply (1 ulp; the parity tolerance of a resampled
+// weight is 5e-5): the staging of the fused coadd evaluates this once per staged pixel.
 __device__ inline float2 prep_pixel(float v, float w, bool has_w, float bg, float var_scale, float wthresh) {
     const float val = v - bg;
-    const bool ok = (val == val);                         // NaN pixels are bad
+    const bool ok = __builtin_isfinite(val);              // NaN and +-inf pixels are bad (one v_cmp_class)
     // (one select per plane: the weight test and the NaN test meet in the scalar condition)
     const bool good = has_w ? (ok && w > wthresh) : ok;
     const float var = has_w ? var_scale * __builtin_amdgcn_rcpf(w) : var_scale;

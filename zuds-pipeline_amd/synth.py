@@ -112,6 +112,44 @@ def make_frame(nx, ny, seed, wcs, sky=150.0, noise=5.0, nstars=40, fwhm=2.0,
                 flxscale=10 ** (-0.4 * (magzp - 25.0)))
 
 
+def add_nonfinite(frame, seed, nscatter=0, values=(np.nan, np.inf, -np.inf), pixels=(), block=None, rows=(),
+                  cols=(), edges=False, weights=None):
+    """A copy of ``frame`` (make_frame's dict) with poisoned pixels; ``frame`` itself is left as it is.
+
+    Into the image: ``nscatter`` pixels drawn with their own generator (``seed``) that cycle through ``values``;
+    ``pixels``: (x, y, value) triples; ``block``: (x0, y0, size, value), a square; ``rows`` / ``cols``: whole rows
+    / columns of NaN; ``edges``: NaN on every pixel of the first and last rows and columns.  ``weights``: (x, y,
+    weight) triples written into the weight plane.  Real frames carry such pixels: ZTF frames have NaN pixels
+    (zuds/constants.py:59) and an rms map is inf on an unmasked zero-weight pixel."""
+    rng = np.random.default_rng(seed)
+    out = dict(frame)
+    img = np.array(frame['img'], copy=True)
+    ny, nx = img.shape
+    if nscatter:
+        xs, ys = rng.integers(0, nx, nscatter), rng.integers(0, ny, nscatter)
+        for k in range(nscatter):
+            img[ys[k], xs[k]] = values[k % len(values)]
+    for x, y, v in pixels:
+        img[y, x] = v
+    if block is not None:
+        x0, y0, n, v = block
+        img[y0:y0 + n, x0:x0 + n] = v
+    for y in rows:
+        img[y, :] = np.nan
+    for x in cols:
+        img[:, x] = np.nan
+    if edges:
+        img[0, :] = img[-1, :] = np.nan
+        img[:, 0] = img[:, -1] = np.nan
+    out['img'] = img
+    if weights:
+        wgt = np.array(frame['wgt'], copy=True)
+        for x, y, w in weights:
+            wgt[y, x] = w
+        out['wgt'] = wgt
+    return out
+
+
 def config1(n=4, nx=512, ny=512):
     """BASELINE config 1: n frames, shared TAN WCS, sky 150 + N(0, 5^2), 40
     stars FWHM 2.0 px, MAGZP 25, one 5x5 bad block (bit 8) per frame."""

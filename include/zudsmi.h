@@ -491,6 +491,66 @@ int zm_star_fwhm_dev(zm_ctx* ctx, const float* img, int nx, int ny, int nstar,
                      const int* x, const int* y, int half, double* out_fwhm,
                      double* out_cx, double* out_cy);
 
+/* ---- source extraction: detection catalog and segmentation map -------------- */
+/* Replaces the SExtractor run of PipelineFITSCatalog.from_image (zuds/catalog.py:96-130) with the
+ * settings of zuds/astromatic/sextractor.conf.  The arithmetic is a chosen convention (DESIGN.md,
+ * "Source extraction"; restated in tests/extract_ref.py):
+ *   a pixel is bad if bad != 0, img or sigma is not finite, or sigma <= 0;
+ *   filter       3 x 3 [1 2 1; 2 4 2; 1 2 1] / 16 (default.conv), bad and outside pixels enter as 0,
+ *                float32 sums in row-major tap order (filter = 0: the image itself);
+ *   foreground   not bad and filtered > (float)detect_thresh * sigma;
+ *   objects      8-connected components of at least detect_minarea pixels, numbered 1 .. n in raster
+ *                order of their first pixel; no deblending, no cleaning;
+ *   measurements isophotal, float64 sums in a fixed order; apertures with zm_aperture_photometry_dev. */
+typedef struct zm_extract_params {
+    float detect_thresh;     /* DETECT_THRESH, in units of sigma (1.5) */
+    float satur_level;       /* SATUR_LEVEL (50000) */
+    int32_t detect_minarea;  /* DETECT_MINAREA (5) */
+    int32_t filter;          /* 1: default.conv (FILTER Y), 0: none (FILTER N) */
+    double aper_radius;      /* PHOT_APERTURES / 2 (3 px) */
+} zm_extract_params;
+void zm_extract_params_default(zm_extract_params* p);
+
+#define ZM_EXTRACT_CHAIN 1       /* status bit: a label chain passed its bound (results are not to be used) */
+
+/* One row of the object table.  Pixel coordinates are 1-based (SExtractor's *_IMAGE). */
+typedef struct zm_object {
+    int32_t number;          /* NUMBER */
+    int32_t npix;            /* ISOAREA_IMAGE */
+    int32_t xmin, xmax, ymin, ymax;   /* XMIN_IMAGE .. YMAX_IMAGE */
+    int32_t flags;           /* FLAGS: 4 saturated, 8 on the frame border, 16 aperture incomplete */
+    int32_t flags_weight;    /* FLAGS_WEIGHT: 1 = a bad pixel touches the object */
+    int32_t imaflags_iso;    /* IMAFLAGS_ISO: OR of the flag plane over the object */
+    int32_t first;           /* 0-based linear index of the object's first pixel in raster order */
+    int32_t nthresh;         /* pixels at or above the level FWHM_IMAGE is measured at */
+    int32_t pad_;
+    double x_image, y_image; /* barycentre of the filtered values */
+    double x2, y2, xy;       /* central second moments */
+    double a_image, b_image, theta_image, elongation;
+    double fwhm_image;
+    double flux_iso, flux_max;   /* unfiltered values */
+    double peak;             /* largest filtered value */
+    double flux_aper, fluxerr_aper;
+    double x_world, y_world; /* NaN without a WCS */
+} zm_object;
+
+/* img, sigma, bad (uint8, may be NULL), flag (int32, may be NULL): device planes of nx x ny pixels.
+ * out_rows: host array of max_objects rows (may be NULL when max_objects is 0).  segm_dev (int32) and
+ * filtered_dev (float32): optional device planes.  More objects than max_objects is not an error: the
+ * first max_objects in NUMBER order are written (*out_nwritten), the segmentation map holds all of them
+ * and *out_nfound is the total.  *out_status (may be NULL): 0, or ZM_EXTRACT_* bits. */
+int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                   const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                   const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                   int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
+                   int* out_status);
+/* The same with host planes (out_segm / out_filtered: host arrays or NULL). */
+int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+               const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+               const zm_extract_params* params, int max_objects, zm_object* out_rows,
+               int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
+               int* out_status);
+
 /* ---- FITS data blocks on the device ------------------------------------------ */
 /* Replaces the host-side decode / encode astropy does inside FITSFile.load_data / save
  * (zuds/fitsfile.py:69-94,146-206): raw_dev holds the big-endian data block of a primary

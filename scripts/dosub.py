@@ -2,10 +2,12 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits
+usage: dosub.py images.txt ref.fits [--detect]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
+With ``--detect`` every subtraction also gets its detection catalog (``sub.*.cat``, FITS_LDAC) and its filtered
+detections (``PipelineFITSCatalog.from_image`` -> ``Detection.from_catalog``, dosub.py:109-131).
 """
 import os
 import sys
@@ -18,11 +20,14 @@ import zuds_amd as zuds
 zuds.init_db()
 
 
+MAX_DETS = 50
+
+
 class PredecessorError(Exception):
     pass
 
 
-def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp'):
+def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -61,24 +66,47 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp'):
     substop = time.time()
     print(f'sub: {substop - substart:.2f} sec to make {sub.basename}', flush=True)
 
+    detections = None
+    if detect:
+        catstart = time.time()
+        cat = zuds.PipelineFITSCatalog.from_image(sub)
+        catstop = time.time()
+        print(f'cat: {catstop - catstart:.2f} sec to make catalog for {sub.basename}', flush=True)
+        dstart = time.time()
+        detections = zuds.Detection.from_catalog(cat, filter=True)
+        if len(detections) > MAX_DETS:
+            raise zuds.TooManyDetectionsError(f'Error: {len(detections)} detections (>{MAX_DETS}) '
+                                              f'on "{sub.basename}", something wrong with the image probably')
+        dstop = time.time()
+        print(f'det: {dstop - dstart:.2f} sec to make detections for {sub.basename}', flush=True)
+
     cleanstart = time.time()
     sci.unmap()
     cleanstop = time.time()
     tstop = time.time()
     print(f'clean: took {cleanstop - cleanstart} sec to clean up after {sub.basename}"', flush=True)
     print(f'took {tstop - tstart} sec to make "{sub.basename}"', flush=True)
+    if detect:
+        return sub, detections
     return sub
 
 
-if __name__ == '__main__':
-    infile = sys.argv[1]
-    refname = sys.argv[2]
+def main(argv):
+    detect = '--detect' in argv
+    args = [a for a in argv if a != '--detect']
+    infile = args[0]
+    refname = args[1]
     subclass = zuds.SingleEpochSubtraction
     sciclass = zuds.ScienceImage
     imgs = zuds.get_my_share_of_work(infile)
     for fn in imgs:
         try:
-            sub = do_one(str(fn), sciclass, subclass, refname)
+            do_one(str(fn), sciclass, subclass, refname, detect=detect)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main(sys.argv[1:]))

@@ -1,0 +1,260 @@
+"""zm_extract (csrc/extract.hip) against the numpy restatement (tests/extract_ref.py) on the GPU.
+
+Integer results (filtered plane, foreground, segmentation map, NUMBER order, areas, boxes, flags) are compared bit for
+bit.  Float columns, three figures each, printed before anything is asserted:
+
+* the order bound: 10 x the largest difference the restatement shows between its forward and its reversed summation
+  order on the same input (``extract_ref.order_bounds``; the aperture sums are reversed too);
+* the allowance for a library function that is not correctly rounded: THETA_IMAGE (atan2) and FWHM_IMAGE (log) get 6
+  spacings of the row's own value, derived in ``extract_ref.LIBM_ULPS``; every other column gets none;
+* the measured GPU - restatement difference.
+
+X_IMAGE, Y_IMAGE, A_IMAGE, B_IMAGE, ELONGATION, FLUX_ISO and FLUX_MAX are asserted against the order bound alone,
+THETA_IMAGE and FWHM_IMAGE against order bound + allowance.  FLUX_APER and FLUXERR_APER are NOT held to the order bound:
+they come from the existing aperture kernel, whose circle / pixel overlap goes through sqrt and asin of differences that
+FMA contraction rounds differently from numpy; they are held to that kernel's existing pin against the same oracle
+function (tests/test_photometry_gpu.py: rtol 1e-10, atol 1e-9), and their order bound is printed beside it.  Rows whose
+restated aperture sum is not finite (a NaN or inf under the aperture) are left out of those two columns; every other
+row is compared, FLAGS 16 or not.
+"""
+import numpy as np
+import pytest
+
+import extract_ref as xr
+from util import synth
+
+pytestmark = pytest.mark.gpu
+
+WORST, ORDER = {}, {}          # per float column over the whole module: largest measured difference, largest order bound
+APER_COLUMNS = ('FLUX_APER', 'FLUXERR_APER')
+
+
+@pytest.fixture(scope='module', autouse=True)
+def report_maxima():
+    yield
+    print('\nextract, whole module: column measured (largest order bound): ' +
+          ', '.join(f'{c} {WORST[c]:.3g} ({ORDER[c]:.3g})' for c in WORST))
+INT_MAP = dict(NUMBER='NUMBER', XMIN_IMAGE='XMIN_IMAGE', XMAX_IMAGE='XMAX_IMAGE', YMIN_IMAGE='YMIN_IMAGE',
+               YMAX_IMAGE='YMAX_IMAGE', ISOAREA_IMAGE='ISOAREA_IMAGE', FLAGS='FLAGS', FLAGS_WEIGHT='FLAGS_WEIGHT',
+               IMAFLAGS_ISO='IMAFLAGS_ISO')
+
+
+def field(nx, ny, seed, nstars=None, noise=3.0, fwhm=2.4, poison=True):
+    """Star field with bad blocks, NaN / inf pixels, zero-noise pixels, flagged pixels, saturated cores and stars on
+    the border."""
+    rng = np.random.default_rng(seed)
+    nstars = nstars if nstars is not None else max(1, nx * ny // 3000)
+    img = rng.normal(0.0, noise, (ny, nx))
+    x, y = rng.uniform(-1, nx, nstars), rng.uniform(-1, ny, nstars)          # some sit on the border
+    flux = 10 ** rng.uniform(np.log10(300.0), np.log10(2e5), nstars)
+    flux[::10] = 5e5                                                          # cores above SATUR_LEVEL
+    synth().add_stars(img, x, y, flux, fwhm)
+    img = img.astype(np.float32)
+    sigma = (noise * rng.uniform(0.8, 1.25, (ny, nx))).astype(np.float32)
+    bad = np.zeros((ny, nx), np.uint8)
+    flag = np.zeros((ny, nx), np.int32)
+    if poison and nx * ny > 30:
+        for _ in range(max(1, nstars // 6)):
+            bx, by = rng.integers(0, nx), rng.integers(0, ny)
+            bad[by:by + 5, bx:bx + 5] = 1
+        npo = max(3, nx * ny // 2000)
+        yy, xx = rng.integers(0, ny, npo), rng.integers(0, nx, npo)
+        img[yy, xx] = np.resize(np.array([np.nan, np.inf, -np.inf], np.float32), npo)
+        yy, xx = rng.integers(0, ny, npo), rng.integers(0, nx, npo)
+        sigma[yy, xx] = np.resize(np.array([0.0, np.nan, -1.0, np.inf], np.float32), npo)
+        yy, xx = rng.integers(0, ny, 4 * npo), rng.integers(0, nx, 4 * npo)
+        flag[yy, xx] = rng.integers(1, 1 << 12, 4 * npo)
+        k = rng.integers(0, nstars, max(1, nstars // 4))                     # bad / flagged pixels inside stars
+        ok = (x[k] > 2) & (x[k] < nx - 3) & (y[k] > 2) & (y[k] < ny - 3)
+        bad[(y[k][ok] + 2).astype(int), x[k][ok].astype(int)] = 1
+        flag[(y[k][ok]).astype(int), (x[k][ok] + 1).astype(int)] |= 1 << 5
+    return img, sigma, bad, flag
+
+
+def compare(engine, img, sigma, bad=None, flag=None, label='', **params):
+    ref_kw = dict(detect_thresh=params.get('detect_thresh', 1.5), detect_minarea=params.get('detect_minarea', 5),
+                  use_filter=params.get('filter', True), satur_level=params.get('satur_level', 50000.0),
+                  aper_radius=params.get('aper_radius', 3.0))
+    got = engine.extract(img, sigma, bad, flag, full=True, **params)
+    ref = xr.extract(img, sigma, bad, flag, **ref_kw)
+    assert got['status'] == 0
+    assert got['filtered'].tobytes() == np.ascontiguousarray(ref['filtered']).tobytes(), 'filtered plane'
+    assert np.array_equal(got['segm'], ref['segm']), 'segmentation map'
+    assert got['nfound'] == len(ref['table'])
+    t, r = got['table'], ref['table']
+    assert len(t) == len(r)
+    for c in INT_MAP:
+        assert np.array_equal(t[c], r[c]), c
+    rev = xr.extract(img, sigma, bad, flag, reverse=True, **ref_kw)['table']
+    bounds = xr.order_bounds(r, rev)
+    worst, fails = {}, []
+    for c in xr.FLOAT_COLUMNS:
+        ok = np.isfinite(r[c])
+        aper = c in APER_COLUMNS
+        if not aper:
+            assert np.array_equal(np.isfinite(t[c]), ok), c
+        diff = np.abs(t[c][ok] - r[c][ok])
+        assert np.isfinite(diff).all(), c
+        allow = 1e-10 * np.abs(r[c][ok]) + 1e-9 if aper else bounds[c] + xr.libm_allowance(c, r[c][ok])
+        worst[c] = float(diff.max()) if ok.any() else 0.0
+        WORST[c] = max(WORST.get(c, 0.0), worst[c])
+        ORDER[c] = max(ORDER.get(c, 0.0), bounds[c])
+        if (diff > allow).any():
+            fails.append((c, worst[c], bounds[c]))
+    print(f'extract {label}: {len(r)} objects; column measured (order bound; libm allowance in spacings): ' +
+          ', '.join(f'{c} {worst[c]:.3g} ({bounds[c]:.3g}; {xr.LIBM_ULPS.get(c, 0)})' for c in xr.FLOAT_COLUMNS))
+    assert not fails, fails
+    return got, ref
+
+
+@pytest.mark.parametrize('shape', [(1, 1), (7, 5), (257, 129), (400, 360), (512, 512)])
+def test_star_fields_with_every_kind_of_bad_pixel(engine, shape):
+    nx, ny = shape
+    img, sigma, bad, flag = field(nx, ny, seed=100 + nx)
+    got, ref = compare(engine, img, sigma, bad, flag, label=f'{nx}x{ny}')
+    if nx >= 257:
+        tab = ref['table']
+        assert len(tab) > 5
+        # the input does exercise the flags
+        assert (tab['FLAGS'] & 8).any() and (tab['FLAGS'] & 16).any() and (tab['FLAGS_WEIGHT'] == 1).any()
+        assert (tab['IMAFLAGS_ISO'] != 0).any()
+        if nx >= 400:
+            assert (tab['FLAGS'] & 4).any()
+
+
+def test_one_by_one_frames(engine):
+    one = np.full((1, 1), 10.0, np.float32)
+    for minarea, n in ((1, 1), (5, 0)):
+        got, ref = compare(engine, one, np.ones_like(one), detect_minarea=minarea, label='1x1')
+        assert len(got['table']) == n and int(got['segm'][0, 0]) == n
+
+
+def test_full_size_frame_once(engine):
+    img, sigma, bad, flag = field(3072, 3080, seed=3, nstars=2500)
+    compare(engine, img, sigma, bad, flag, label='3072x3080')
+
+
+def test_without_planes_and_without_filter(engine):
+    img, sigma, bad, flag = field(300, 200, seed=8)
+    compare(engine, img, sigma, None, None, label='no bad, no flag')
+    compare(engine, img, sigma, bad, flag, filter=False, label='FILTER N')
+    compare(engine, img, sigma, bad, flag, detect_thresh=3.0, detect_minarea=2, satur_level=5000.0, aper_radius=4.5,
+            label='other parameters')
+
+
+def spiral(n):
+    """A one-pixel-wide square spiral with one-pixel gaps that fills an n x n frame."""
+    a = np.zeros((n, n), bool)
+    x0, y0, x1, y1 = 0, 0, n - 1, n - 1
+    a[y0, x0:x1 + 1] = True
+    while True:
+        a[y0:y1 + 1, x1] = True
+        a[y1, x0:x1 + 1] = True
+        y0 += 2
+        if y0 > y1:
+            break
+        a[y0:y1 + 1, x0] = True
+        x1 -= 2
+        if x1 < x0:
+            break
+        a[y0, x0:x1 + 1] = True
+        y1 -= 2
+        x0 += 2
+        if y0 > y1 or x0 > x1:
+            break
+    return a
+
+
+def comb(n):
+    a = np.zeros((n, n), bool)
+    a[:, ::2] = True                      # teeth two columns apart: they meet only along the bottom row
+    a[n - 1, :] = True
+    return a
+
+
+SHAPES = {
+    'spiral': lambda n: spiral(n),
+    'comb': lambda n: comb(n),
+    'checkerboard': lambda n: (np.add.outer(np.arange(n), np.arange(n)) % 2 == 0),
+    'all_above': lambda n: np.ones((n, n), bool),
+    'nothing_above': lambda n: np.zeros((n, n), bool),
+}
+
+
+@pytest.mark.parametrize('name', list(SHAPES))
+def test_adversarial_shapes_for_the_labelling(engine, name):
+    """Long equivalence chains across every tile.  FILTER N so that the drawn shape is the foreground itself."""
+    n = 512
+    shape = SHAPES[name](n)
+    img = np.where(shape, 100.0, 0.0).astype(np.float32)
+    got, ref = compare(engine, img, np.ones_like(img), filter=False, label=name)
+    assert np.array_equal(ref['fg'], shape)
+    if name == 'nothing_above':
+        assert len(got['table']) == 0 and not got['segm'].any()
+    else:
+        assert len(got['table']) == 1 and got['table']['ISOAREA_IMAGE'][0] == shape.sum()
+        t = got['table'][0]
+        assert (t['XMIN_IMAGE'], t['XMAX_IMAGE'], t['YMIN_IMAGE'], t['YMAX_IMAGE']) == (1, n, 1, n)
+
+
+def test_adversarial_shapes_through_the_filter(engine):
+    for name in ('spiral', 'checkerboard'):
+        img = np.where(SHAPES[name](512), 100.0, 0.0).astype(np.float32)
+        compare(engine, img, np.ones_like(img), label=name + ' filtered')
+
+
+def test_all_bad_frame(engine):
+    img = np.full((64, 96), 100.0, np.float32)
+    got, ref = compare(engine, img, np.ones_like(img), np.ones(img.shape, np.uint8), label='all bad')
+    assert len(got['table']) == 0 and not got['segm'].any()
+    got, ref = compare(engine, np.full((64, 96), np.nan, np.float32), np.ones_like(img), label='all NaN')
+    assert len(got['table']) == 0
+
+
+def test_two_runs_give_the_same_bytes(engine):
+    img, sigma, bad, flag = field(700, 500, seed=21)
+    a = engine.extract(img, sigma, bad, flag, full=True)
+    b = engine.extract(img, sigma, bad, flag, full=True)
+    assert len(a['table']) > 20
+    assert a['table'].tobytes() == b['table'].tobytes()
+    assert a['segm'].tobytes() == b['segm'].tobytes() and a['filtered'].tobytes() == b['filtered'].tobytes()
+
+
+def test_fewer_rows_than_objects(engine):
+    img, sigma, bad, flag = field(400, 360, seed=33)
+    full = engine.extract(img, sigma, bad, flag, full=True)
+    n = len(full['table'])
+    assert n > 12
+    part = engine.extract(img, sigma, bad, flag, full=True, max_objects=7)
+    assert len(part['table']) == 7 and part['nfound'] == n and part['status'] == 0
+    assert part['table'].tobytes() == full['table'][:7].tobytes()
+    assert np.array_equal(part['segm'], full['segm'])
+    none = engine.extract(img, sigma, bad, flag, full=True, max_objects=0)
+    assert len(none['table']) == 0 and none['nfound'] == n and np.array_equal(none['segm'], full['segm'])
+
+
+def test_world_coordinates_and_device_planes(engine, zuds):
+    import importlib
+    hipmem = importlib.import_module('zuds-pipeline_amd.hipmem')
+    img, sigma, bad, flag = field(320, 240, seed=41)
+    w = synth().ztf_wcs(320, 240, tpv=True)
+    tab, segm = engine.extract(img, sigma, bad, flag, wcs=w)
+    ra, dec = w.all_pix2world(tab['X_IMAGE'], tab['Y_IMAGE'], 1)
+    assert np.array_equal(tab['X_WORLD'], ra) and np.array_equal(tab['Y_WORLD'], dec)
+    bufs = []
+    for a in (img, sigma, bad, flag):
+        b = hipmem.DeviceBuffer(a.nbytes)
+        b.upload(a)
+        bufs.append(b)
+    dseg = hipmem.DeviceBuffer(segm.nbytes)
+    dtab, nfound = engine.extract_dev(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, 320, 240, wcs=w, segm=dseg.ptr)
+    assert nfound == len(tab) and dtab.tobytes() == tab.tobytes()
+    assert np.array_equal(dseg.download(np.int32, segm.shape), segm)
+
+
+def test_bad_arguments_set_the_last_error(engine, zuds):
+    L = zuds._lib.lib()
+    assert L.zm_extract(engine.ctx, None, None, None, None, 4, 4, None, None, 0, None, None, None, None, None, None) != 0
+    assert b'zm_extract' in L.zm_last_error()
+    with pytest.raises(zuds.ZMError, match='bad parameters'):
+        engine.extract(np.zeros((4, 4), np.float32), np.ones((4, 4), np.float32), detect_thresh=-1.0)

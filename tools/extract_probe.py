@@ -1,0 +1,143 @@
+#!/usr/bin/env python
+"""Time the source extractor on a resident difference image of the bench's synthetic step.
+
+    python tools/extract_probe.py [--size 3072] [--frames 8] [--steps 20] [--out FILE.json]
+
+Builds the bench's synthetic science epoch and a reference coadded from ``--frames`` of its frames (bench.py's
+``make_device_frames`` and defect mask), runs the device-resident subtraction, then times on the same stream, with HIP
+events, per call:
+
+* ``subtract_ms``  the subtraction leg (``DeviceSubtraction.run``);
+* ``extract_ms``   ``DeviceSubtraction.extract`` on the resident difference, noise and mask planes (object table to the
+  host included);
+* ``copy_ms``      a float4 copy (``zm_copy_probe_dev``) that moves the bytes of the planes the extractor has to touch
+  at least once: image, noise, flag plane, segmentation map (4 B per pixel each) and the bad-pixel map (1 B).  The copy
+  cycles through four source / destination pairs (640 MB in all at the default size), more than the 256 MB last-level
+  cache holds, so that no call finds its source there from the call before;
+* ``whole_frame_object_ms``  one extraction of a frame that is a single object (every pixel above the threshold): the
+  worst case of the per-object walk, one workgroup over the whole bounding box.
+
+The frame is square because the bench's synthetic frames are (``bench.make_device_frames``).
+
+Prints one JSON line with the three clocks and the two ratios.  For the per-kernel table run it under
+``rocprofv3 --kernel-trace --stats -- python tools/extract_probe.py --steps 5``.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--size', type=int, default=3072)
+    ap.add_argument('--frames', type=int, default=8)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    import torch
+    import bench
+    z = importlib.import_module('zuds-pipeline_amd')
+    synth = importlib.import_module('zuds-pipeline_amd.synth')
+    dev = importlib.import_module('zuds-pipeline_amd.device')
+    check = z._lib.check
+    device = torch.device('cuda', 0)
+    torch.cuda.set_device(0)
+    eng = z.Engine(0)
+    size = args.size
+    base, frames = bench.make_device_frames(synth, torch, args.frames + 1, size, 2000, device, 'int16')
+    sci = frames.pop()
+    g = torch.Generator(device='cpu')
+    g.manual_seed(77)
+    bx = torch.randint(2, size - 2, (300,), generator=g)
+    by = torch.randint(2, size - 2, (300,), generator=g)
+    smask = torch.zeros((size, size), dtype=torch.int16)
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            smask[by + dy, bx + dx] = 256
+    sci['mask'] = smask.to(device)
+    sci['wgt'] = torch.where(sci['mask'] != 0, 0.0, float(sci['wgt'].max())).to(torch.float32)
+    sci['rms'] = torch.where(sci['wgt'] > 0, 1.0 / torch.sqrt(sci['wgt'].clamp_min(1e-20)),
+                             float(np.sqrt(50000.0))).to(torch.float32)
+    params = z.coadd_params(combine='CLIPPED', subtract_back=True, rescale_weights=True)
+    coadd = dev.DeviceCoadd(base, params, device=0, engine=eng, want_mask=True)
+    sub = dev.DeviceSubtraction(sci['wcs'], base, device=0, engine=eng, stream=coadd.stream)
+    npx = coadd.img.numel()
+    ref_rms = torch.empty_like(coadd.wgt)
+    coadd.run(dev.DeviceFrames(frames, device))
+    with torch.cuda.stream(coadd.stream):
+        check(eng.L.zm_mask_flag_dev(eng.ctx, coadd.mask.data_ptr(), coadd.mask_wgt.data_ptr(), 0.0, 1 << 16, npx))
+        check(eng.L.zm_add_scalar_dev(eng.ctx, coadd.img.data_ptr(), 150.0, npx))
+        check(eng.L.zm_rms_from_weight_dev(eng.ctx, coadd.wgt.data_ptr(), None, npx, float(np.sqrt(50000.0)),
+                                           ref_rms.data_ptr()))
+    seeing = 4.0                      # bench.py --seeing default
+
+    def subtract():
+        sub.run(sci['img'], sci['rms'], sci['mask'], sci['wgt'], coadd.img, ref_rms, coadd.mask, seeing=seeing, nreg_side=3)
+
+    found = {}
+
+    def extract():
+        tab, nfound, _ = sub.extract()
+        found['n'] = nfound
+
+    nbytes = (17 * size * size // 2) // 16 * 16
+    pairs = [(torch.zeros(nbytes, dtype=torch.uint8, device=device), torch.empty(nbytes, dtype=torch.uint8, device=device))
+             for _ in range(4)]
+    turn = [0]
+
+    def copy():
+        src, dst = pairs[turn[0] % len(pairs)]
+        turn[0] += 1
+        check(eng.L.zm_copy_probe_dev(eng.ctx, src.data_ptr(), dst.data_ptr(), nbytes))
+
+    def clock(fn):
+        with torch.cuda.stream(coadd.stream):
+            for _ in range(args.warmup):
+                fn()
+            times = []
+            for _ in range(args.steps):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(coadd.stream)
+                fn()
+                b.record(coadd.stream)
+                b.synchronize()
+                times.append(a.elapsed_time(b))
+        return float(np.median(times)), float(np.min(times))
+
+    s_med, s_min = clock(subtract)
+    e_med, e_min = clock(extract)
+    c_med, c_min = clock(copy)
+    flat = torch.full((size, size), 100.0, dtype=torch.float32, device=device)
+    one = torch.ones((size, size), dtype=torch.float32, device=device)
+    torch.cuda.synchronize()
+
+    def whole():
+        tab, nfound = eng.extract_dev(flat.data_ptr(), one.data_ptr(), None, None, size, size, filter=False)
+        assert nfound == 1 and tab['ISOAREA_IMAGE'][0] == size * size
+    args.steps, args.warmup, keep = 3, 1, (args.steps, args.warmup)
+    w_med, _ = clock(whole)
+    args.steps, args.warmup = keep
+    out = dict(size=size, whole_frame_object_ms=round(w_med, 3), frames=args.frames, steps=args.steps, objects=found.get('n'),
+               subtract_ms=round(s_med, 4), subtract_ms_min=round(s_min, 4),
+               extract_ms=round(e_med, 4), extract_ms_min=round(e_min, 4),
+               copy_ms=round(c_med, 4), copy_bytes_per_pixel=17,
+               extract_over_subtract=round(e_med / s_med, 3), extract_over_copy=round(e_med / c_med, 2))
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

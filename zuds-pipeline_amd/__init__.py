@@ -23,7 +23,10 @@ from .subtraction import *
 from .mpi import *
 from .photometry import *
 from .seeing import *
+from .extract import *
 from .filterobjects import *
+from .catalog import *
+from .detections import *
 from . import synth, fits
 
 # same DB-free entry points as the reference

@@ -93,6 +93,25 @@ class zm_mask_plan(C.Structure):
                 ('gather_off', C.c_int64 * COMM_MAX_RANKS)]
 
 
+class zm_extract_params(C.Structure):
+    _fields_ = [('detect_thresh', C.c_float), ('satur_level', C.c_float),
+                ('detect_minarea', C.c_int32), ('filter', C.c_int32),
+                ('aper_radius', C.c_double)]
+
+
+class zm_object(C.Structure):
+    """One row of the object table of ``zm_extract`` (include/zudsmi.h)."""
+    _fields_ = [('number', C.c_int32), ('npix', C.c_int32), ('xmin', C.c_int32), ('xmax', C.c_int32),
+                ('ymin', C.c_int32), ('ymax', C.c_int32), ('flags', C.c_int32), ('flags_weight', C.c_int32),
+                ('imaflags_iso', C.c_int32), ('first', C.c_int32), ('nthresh', C.c_int32), ('pad_', C.c_int32),
+                ('x_image', C.c_double), ('y_image', C.c_double), ('x2', C.c_double), ('y2', C.c_double),
+                ('xy', C.c_double), ('a_image', C.c_double), ('b_image', C.c_double), ('theta_image', C.c_double),
+                ('elongation', C.c_double), ('fwhm_image', C.c_double), ('flux_iso', C.c_double),
+                ('flux_max', C.c_double), ('peak', C.c_double), ('flux_aper', C.c_double),
+                ('fluxerr_aper', C.c_double), ('x_world', C.c_double), ('y_world', C.c_double)]
+
+
+EXTRACT_CHAIN = 1                                      # zm_extract status bit (ZM_EXTRACT_CHAIN)
 HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4          # zm_hp_info.status bits (include/zudsmi.h)
 
 
@@ -193,6 +212,11 @@ _SIGS = {
                                          C.c_double, _P, _P, _P]),
     'zm_aperture_photometry_dev': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P,
                                              C.c_double, _P, _P, _P]),
+    'zm_extract_params_default': (None, [C.POINTER(zm_extract_params)]),
+    'zm_extract_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
+                                 C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'zm_extract': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
+                             C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'zm_timing_enable': (C.c_int, [_P, C.c_int]),
     'zm_timing_filter': (C.c_int, [_P, C.c_char_p]),
     'zm_timing_reset': (C.c_int, [_P]),

@@ -18,7 +18,7 @@ LIBNAME = 'libzudsmi.so'
 OBJDIR = LIBDIR / 'build'
 
 SOURCES = ['ctx.hip', 'wcs_host.hip', 'resample.hip', 'resample_opts.hip', 'maskbox.hip', 'fused_host.hip', 'fused_dma.hip', 'fused_own.hip', 'combine.hip',
-           'background.hip', 'api_coadd.hip', 'hotpants.hip', 'hp_vectors.hip', 'hp_apply.hip', 'api_subtract.hip', 'select_bracket.hip', 'elementwise.hip', 'photometry.hip', 'fitsio.hip', 'detect.hip', 'comm.hip']
+           'background.hip', 'api_coadd.hip', 'hotpants.hip', 'hp_vectors.hip', 'hp_apply.hip', 'api_subtract.hip', 'select_bracket.hip', 'elementwise.hip', 'photometry.hip', 'fitsio.hip', 'detect.hip', 'extract.hip', 'comm.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
          '-Wno-unused-result']
 # the device assembly of every translation unit stays next to its object (build/<stem>-hip-amdgcn-amd-amdhsa-gfx950.s):
@@ -52,7 +52,11 @@ def lint_built(objdir, sources, verbose=True):
     """isa_checks on the device assembly of the translation units that were just compiled - the instructions that
     went into the objects, under the flags of this build (ZM_HIPCC_FLAGS included).  A finding fails the build: the
     object is removed so that the next build compiles and checks it again."""
-    from . import isa_checks
+    try:
+        from . import isa_checks
+    except ImportError:                                   # run as a script (python zuds-pipeline_amd/build.py)
+        sys.path.insert(0, str(HERE))
+        import isa_checks
     findings = []
     for src in sources:
         asm = device_asm(objdir, src)

@@ -236,6 +236,25 @@ class DeviceSubtraction(object):
             self.check_limits()
         return self.info
 
+    def extract(self, wcs=None, max_objects=None, **params):
+        """Detection catalog of the resident difference image (``Engine.extract_dev``): noise plane as sigma, the
+        subtraction mask as flag plane, its ``BAD_SUM`` pixels as bad pixels; nothing but the object table crosses to
+        the host.  No background pass: hotpants' difference image carries none.  ``wcs``: the science grid unless
+        given.  Returns (table, number found, segmentation map as an int32 tensor)."""
+        torch = self.torch
+        self.result()
+        ny, nx = self.shape
+        kw = dict(params)
+        if max_objects is not None:
+            kw['max_objects'] = max_objects
+        with torch.cuda.stream(self.stream):
+            bad = ((self.submask & self.BAD_SUM) != 0).to(torch.uint8)
+            segm = torch.empty(self.shape, dtype=torch.int32, device=self.device)
+            tab, nfound = self.engine.extract_dev(self.diff.data_ptr(), self.noise.data_ptr(), bad.data_ptr(),
+                                                  self.submask.data_ptr(), nx, ny,
+                                                  wcs=self.wsci if wcs is None else wcs, segm=segm.data_ptr(), **kw)
+        return tab, nfound, segm
+
     def release_overlap(self):
         """Give the second context of ``overlap=True`` back (it is made again on the next run that wants it)."""
         if self._bk_engine is not None:

@@ -390,3 +390,6 @@ def hp_params(**kw):
         else:
             raise ValueError(f'unknown hotpants parameter "{k}"')
     return p
+
+
+from . import extract as _extract  # noqa: E402,F401  (Engine.extract / Engine.extract_dev)

@@ -1,23 +1,28 @@
-"""Pixel-level cuts of the reference's candidate filter.
+"""The reference's candidate filter.
 
-``filter_sexcat`` (``zuds/filterobjects.py:57-195``) mixes SExtractor catalog columns with
-three tests that need only pixels; those three are computed here on the GPU for any list of
-positions (``X_IMAGE``, ``Y_IMAGE``: 1-based, as SExtractor reports them):
+``filter_sexcat`` (``zuds/filterobjects.py:57-195``) mixes cuts on catalog columns with
+three tests that need only pixels; those three are computed on the GPU for any list of
+positions (``X_IMAGE``, ``Y_IMAGE``: 1-based, as SExtractor reports them) by ``pixel_cuts``:
 
 * ``BPMCUT``  exact-overlap aperture sum (r = 6 px) of the boolean bad-pixel map; must be 0;
 * ``RMSCUT``  aperture sum of the rms map / (pi 6^2); must not exceed 1.1 x the median rms of
   the good pixels;
 * negative-pixel cut: a pixel of the 11 x 11 cutout below -5 sigma with a 3 x 3 neighbour above
   +5 sigma, sigma = 1.48 x MAD of the image about its median (``filterobjects.py:155-162``).
+
+``filter_sexcat(cat)`` is the whole filter on a ``PipelineFITSCatalog``: the column cuts in the reference's order,
+then the pixel cuts.  The braai CNN score is not computed: ``rb`` is -99 for every row, as the reference leaves it
+for rows that never reach the network.
 """
 import ctypes as C
 
 import numpy as np
 
 from ._lib import check, ptr
+from .constants import BAD_SUM
 from .engine import get_engine
 
-__all__ = ['pixel_cuts', 'CUTSIZE']
+__all__ = ['pixel_cuts', 'column_cuts', 'filter_sexcat', 'CUTSIZE']
 
 CUTSIZE = 11          # pixels, zuds/filterobjects.py:12
 CUT_RADIUS = 6.0      # zuds/filterobjects.py:102-104
@@ -52,3 +57,59 @@ def pixel_cuts(data, rms, bpm, x_image, y_image, engine=None):
     rmscut = rmsbig / area
     good = (bpmbig <= 0) & (rmscut <= medcut) & (neg == 0)
     return dict(BPMCUT=bpmbig, RMSCUT=rmscut, MEDCUT=medcut, NEGPIX=neg, GOODCUT=good.astype(np.uint8))
+
+
+def column_cuts(table, see, bpmcut, rmscut, medcut):
+    """GOODCUT (uint8) after the reference's catalog-column cuts, in its order (``zuds/filterobjects.py:125-148``),
+    and the number of candidates left after each of them."""
+    good = np.ones(len(table), dtype=np.uint8)
+    left = []
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for name, fails in (('external flag', (table['IMAFLAGS_ISO'] & BAD_SUM) > 0),
+                            ('internal flag', table['FLAGS'] > 2),
+                            ('elipticity', table['A_IMAGE'] / table['B_IMAGE'] > 2.0),
+                            ('fwhm', table['FWHM_IMAGE'] / see > 2.0),
+                            ('sharp', table['FWHM_IMAGE'] < 0.8 * see),
+                            ('bpm', np.asarray(bpmcut) > 0),
+                            ('rms', np.asarray(rmscut) > medcut),
+                            ('s/n > 5', table['FLUX_APER'] / table['FLUXERR_APER'] < 5)):
+            good[np.where(fails)] = 0
+            left.append((name, int(good.sum())))
+    return good, left
+
+
+def _append_columns(table, **cols):
+    out = np.zeros(len(table), dtype=table.dtype.descr + [(k, np.asarray(v).dtype.str) for k, v in cols.items()])
+    for n in table.dtype.names:
+        out[n] = table[n]
+    for k, v in cols.items():
+        out[k] = v
+    return out.view(np.recarray)
+
+
+def filter_sexcat(cat, engine=None, quiet=False):
+    """Filter the catalog of a subtraction (``zuds/filterobjects.py:57-246``): adds ``GOODCUT``, ``BPMCUT``,
+    ``RMSCUT`` and ``rb`` (-99: the CNN step is skipped) columns and saves the catalog.  A catalog that already has a
+    ``GOODCUT`` column is returned as it is."""
+    say = (lambda *a, **k: None) if quiet else print
+    if 'GOODCUT' in cat.data.dtype.names:
+        return cat
+    image = cat.image
+    rms = image.rms_image.data
+    bpm = image.mask_image.boolean.data
+    table = cat.data
+    say('Total number of candidates: ', len(table))
+    if 'SEEING' not in image.header:
+        from .seeing import estimate_seeing
+        estimate_seeing(image)
+    see = image.header['SEEING']
+    pix = pixel_cuts(image.data, rms, bpm, table['X_IMAGE'], table['Y_IMAGE'], engine=engine)
+    good, left = column_cuts(table, see, pix['BPMCUT'], pix['RMSCUT'], pix['MEDCUT'])
+    for name, n in left:
+        say(f'Number of candidates after {name} cut: ', n)
+    good[pix['NEGPIX'] != 0] = 0
+    say('Number of candidates after negpix cut: ', int(good.sum()))
+    cat.data = _append_columns(table, GOODCUT=good, BPMCUT=pix['BPMCUT'], RMSCUT=pix['RMSCUT'],
+                               rb=np.full(len(table), -99.0))
+    cat.save()
+    return cat

@@ -1,10 +1,14 @@
-"""Dependency-free single-HDU FITS image reader / writer.
+"""Dependency-free single-HDU FITS image reader / writer, and the FITS_LDAC catalog layout.
 
 The reference reads and writes its products with ``astropy.io.fits``
 (``zuds/fitsfile.py:69-94,146-178``); astropy is not available on the GPU box, and
 this path only ever touches primary-HDU images (``_DATA_HDU = _HEADER_HDU = 0``,
 ``zuds/fitsfile.py:37-38``).  FITS standard 4.0: 2880-byte blocks, 80-character
 cards, big-endian data, BITPIX 8 / 16 / 32 / 64 / -32 / -64, BSCALE / BZERO.
+
+Catalogs (``PipelineFITSCatalog``, ``_DATA_HDU = 2``, ``zuds/catalog.py:90-93``) are FITS_LDAC files: an empty
+primary HDU, ``LDAC_IMHEAD`` (the image header as one string column) and ``LDAC_OBJECTS`` (a binary table of
+fixed-width scalar columns).  ``write_ldac`` / ``read_ldac`` do exactly that and nothing more general.
 """
 import numpy as np
 
@@ -54,7 +58,7 @@ def _parse_value(s):
         return v, comment
 
 
-def _read_header(read, what):
+def _read_header(read, what, primary=True):
     header, comments = {}, {}
     nblocks = 0
     done = False
@@ -76,7 +80,10 @@ def _read_header(read, what):
                 continue
             header[key] = val
             comments[key] = com
-    if header.get('SIMPLE') is not True:
+    if not primary:
+        if 'XTENSION' not in header:
+            raise ValueError(f'{what}: not a FITS extension (no XTENSION card)')
+    elif header.get('SIMPLE') is not True:
         raise ValueError(f'{what}: not a standard FITS file (SIMPLE != T)')
     return header, comments, nblocks * BLOCK
 
@@ -264,3 +271,87 @@ def write(path, data, header=None, comments=None):
         f.write(hdr)
         f.write(raw)
         f.write(b'\0' * (-len(raw) % BLOCK))
+
+
+# ---- FITS_LDAC ------------------------------------------------------------------------------------------------
+_TFORM = {'u1': 'B', 'i2': 'I', 'i4': 'J', 'i8': 'K', 'f4': 'E', 'f8': 'D'}
+_TFORM_DTYPE = {v: '>' + k for k, v in _TFORM.items()}
+
+
+def _table_hdu(extname, ncols_cards, row_bytes, nrows, body, extra=()):
+    cards = [_card('XTENSION', 'BINTABLE', 'binary table extension'), _card('BITPIX', 8), _card('NAXIS', 2),
+             _card('NAXIS1', int(row_bytes), 'bytes per row'), _card('NAXIS2', int(nrows), 'rows'),
+             _card('PCOUNT', 0), _card('GCOUNT', 1)] + ncols_cards + [_card('EXTNAME', extname)]
+    cards += [_card(k, v, c) for k, v, c in extra]
+    cards.append('END'.ljust(80))
+    hdr = ''.join(cards).encode('ascii', 'replace')
+    return hdr + b' ' * (-len(hdr) % BLOCK) + body + b'\0' * (-len(body) % BLOCK)
+
+
+def write_ldac(path, table, image_header=None, image_comments=None, extra=()):
+    """``table``: numpy structured array of scalar columns (uint8, int16 / 32 / 64, float32 / 64; bool is stored as
+    uint8).  ``image_header``: the header of the image the catalog was made from (LDAC_IMHEAD).  ``extra``:
+    (key, value, comment) cards for the LDAC_OBJECTS header."""
+    table = np.asarray(table)
+    names = table.dtype.names
+    cols, fields = [], []
+    for i, name in enumerate(names, 1):
+        dt = table.dtype[name]
+        if dt.shape:
+            raise ValueError(f'column {name}: only scalar columns')
+        code = 'u1' if dt.kind == 'b' else dt.kind + str(dt.itemsize)
+        if code not in _TFORM:
+            raise ValueError(f'column {name}: dtype {dt} has no FITS_LDAC column type here')
+        fields.append((name, '>' + code))
+        cols += [_card(f'TTYPE{i}', name), _card(f'TFORM{i}', '1' + _TFORM[code])]
+    big = np.empty(len(table), dtype=fields)
+    for name in names:
+        big[name] = table[name]
+    objects = _table_hdu('LDAC_OBJECTS', [_card('TFIELDS', len(names))] + cols, big.dtype.itemsize, len(table),
+                         big.tobytes(), extra)
+    head = header_block((), 8, image_header, image_comments)
+    ncards = len(head) // 80
+    imhead = _table_hdu('LDAC_IMHEAD', [_card('TFIELDS', 1), _card('TTYPE1', 'Field Header Card'),
+                                        _card('TFORM1', f'{len(head)}A'), _card('TDIM1', f'(80, {ncards})')],
+                        len(head), 1, head)
+    primary = ''.join([_card('SIMPLE', True, 'conforms to FITS standard'), _card('BITPIX', 8), _card('NAXIS', 0),
+                       _card('EXTEND', True), 'END'.ljust(80)]).encode('ascii')
+    with open(path, 'wb') as f:
+        f.write(primary + b' ' * (-len(primary) % BLOCK))
+        f.write(imhead)
+        f.write(objects)
+
+
+def read_ldac(path):
+    """(table as a native-endian record array, LDAC_OBJECTS header, image header dict, image header comments)."""
+    with open(path, 'rb') as f:
+        h0, _, _ = _read_header(f.read, path)
+        if int(h0.get('NAXIS', 0)) != 0:
+            raise ValueError(f'{path}: a FITS_LDAC file has an empty primary HDU')
+        found = {}
+        for want in ('LDAC_IMHEAD', 'LDAC_OBJECTS'):
+            h, _, _ = _read_header(f.read, path, primary=False)
+            if h.get('XTENSION') != 'BINTABLE' or h.get('EXTNAME') != want:
+                raise ValueError(f'{path}: expected the {want} binary table, found {h.get("EXTNAME")!r}')
+            nbytes = int(h['NAXIS1']) * int(h['NAXIS2']) + int(h.get('PCOUNT', 0))
+            body = f.read(nbytes)
+            if len(body) != nbytes:
+                raise ValueError(f'{path}: truncated {want} table')
+            f.read(-nbytes % BLOCK)
+            found[want] = (h, body)
+    ih, ic = parse_header(found['LDAC_IMHEAD'][1])
+    h, body = found['LDAC_OBJECTS']
+    fields = []
+    for i in range(1, int(h['TFIELDS']) + 1):
+        form = str(h[f'TFORM{i}']).strip()
+        code = form.lstrip('1')
+        if code not in _TFORM_DTYPE or form not in (code, '1' + code):
+            raise ValueError(f'{path}: column {h[f"TTYPE{i}"]} has TFORM {form}: only scalar B I J K E D columns')
+        fields.append((str(h[f'TTYPE{i}']).strip(), _TFORM_DTYPE[code]))
+    big = np.frombuffer(body, dtype=fields, count=int(h['NAXIS2']))
+    if big.dtype.itemsize != int(h['NAXIS1']):
+        raise ValueError(f'{path}: NAXIS1 {h["NAXIS1"]} does not match the columns ({big.dtype.itemsize} bytes)')
+    native = np.empty(len(big), dtype=[(n, np.dtype(t).newbyteorder('=')) for n, t in fields])
+    for n, _ in fields:
+        native[n] = big[n]
+    return native.view(np.recarray), h, ih, ic

@@ -34,16 +34,21 @@ class CalibratableImageBase(FITSImage):
     field = ccdid = qid = fid = None
 
     def _call_source_extractor(self, checkimage_type=None, tmpdir='/tmp',
-                               use_weightmap=True, sextractor_kws=None):
-        """Produce the requested check-images (``zuds/image.py:103-134``)."""
+                               use_weightmap=True, sextractor_kws=None, catalog=False):
+        """Produce the requested check-images and, with ``catalog=True``, the detection catalog
+        (``zuds/image.py:103-134``)."""
         from . import sextractor
         results = sextractor.run_sextractor(self, checkimage_type=checkimage_type,
                                             tmpdir=tmpdir, use_weightmap=use_weightmap,
-                                            sextractor_kws=sextractor_kws)
+                                            sextractor_kws=sextractor_kws, catalog=catalog)
         for result in results:
-            if result is None:          # the catalog slot (no source extraction on this path)
+            if result is None:          # the catalog slot of a call that asked for check-images only
                 continue
-            if result.basename.endswith('.rms.fits'):
+            if result.basename.endswith('.cat'):
+                self.catalog = result
+            elif result.basename.endswith('.segm.fits'):
+                self._segmimg = result
+            elif result.basename.endswith('.rms.fits'):
                 self._rmsimg = result
             elif result.basename.endswith('.bkgsub.fits'):
                 self._bkgsubimg = result

@@ -1,8 +1,16 @@
-"""Mesh background / rms check-images (``zuds/sextractor.py``).
+"""Check-images and detection catalogs (``zuds/sextractor.py``).
 
-Only the check-images are on this path (``BACKGROUND_RMS``, ``-BACKGROUND``,
-``BACKGROUND``; ``zuds/sextractor.py:21-26``); catalog extraction is out of
-scope.  The SExtractor process is replaced by ``zm_background``.
+The SExtractor process is replaced by libzudsmi: ``zm_background`` for the mesh background / rms check-images
+(``BACKGROUND_RMS``, ``-BACKGROUND``, ``BACKGROUND``; ``zuds/sextractor.py:21-26``) and ``zm_extract`` for the
+catalog and the ``SEGMENTATION`` check-image.  A default call produces check-images only (catalog slot ``None``, no
+extraction work): that is what the coadd / subtraction path asks for.  ``catalog=True`` (or a ``segm`` request)
+runs the extractor with the operator of ``sextractor.conf`` as DESIGN.md ("Source extraction") states it:
+filter ``default.conv``, ``DETECT_THRESH`` 1.5, ``DETECT_MINAREA`` 5, no deblending, no cleaning.
+
+``sextractor_kws``: ``DETECT_THRESH``, ``DETECT_MINAREA``, ``FILTER``, ``PHOT_APERTURES`` (one diameter),
+``SATUR_LEVEL``, ``BACK_SIZE``, ``BACK_FILTERSIZE`` are honoured; keys that would change something this version does
+not do (``DEBLEND_*``, ``CLEAN*``, ``MASK_TYPE``, ``FILTER_NAME``, a ``WEIGHT_TYPE`` other than ``MAP_WEIGHT``, an
+``ANALYSIS_THRESH`` different from ``DETECT_THRESH``) raise ``ValueError``; bookkeeping keys are ignored.
 """
 import os
 
@@ -10,11 +18,50 @@ import numpy as np
 
 from .constants import BAD_SUM, BKG_BOX_SIZE, MASK_BORDER
 
-__all__ = ['prepare_sextractor', 'run_sextractor']
+__all__ = ['prepare_sextractor', 'run_sextractor', 'extraction_settings']
 
 checkimage_map = {'rms': 'BACKGROUND_RMS', 'segm': 'SEGMENTATION',
                   'bkgsub': '-BACKGROUND', 'bkg': 'BACKGROUND'}
-_SUPPORTED = ['rms', 'bkgsub', 'bkg']
+_SUPPORTED = ['rms', 'bkgsub', 'bkg']         # what 'all' stands for: the check-images of the background run
+_EXTRACTION = ['segm']                         # check-images that need the extractor
+
+_HONOURED = ('DETECT_THRESH', 'DETECT_MINAREA', 'FILTER', 'PHOT_APERTURES', 'SATUR_LEVEL', 'BACK_SIZE',
+             'BACK_FILTERSIZE', 'ANALYSIS_THRESH', 'WEIGHT_TYPE')
+_REFUSED_PREFIXES = ('DEBLEND_', 'CLEAN')
+_REFUSED = ('MASK_TYPE', 'FILTER_NAME')
+_IGNORED = ('CATALOG_NAME', 'CATALOG_TYPE', 'PARAMETERS_NAME', 'CHECKIMAGE_TYPE', 'CHECKIMAGE_NAME', 'WEIGHT_IMAGE',
+            'FLAG_IMAGE', 'FLAG_TYPE', 'VERBOSE_TYPE', 'NTHREADS', 'MEMORY_OBJSTACK', 'MEMORY_PIXSTACK',
+            'MEMORY_BUFSIZE', 'STARNNW_NAME', 'WRITE_XML', 'XML_NAME', 'HEADER_SUFFIX', 'MAG_ZEROPOINT', 'GAIN',
+            'GAIN_KEY', 'PIXEL_SCALE', 'SEEING_FWHM', 'SATUR_KEY', 'INTERP_TYPE', 'INTERP_MAXXLAG', 'INTERP_MAXYLAG')
+
+
+def _yes(v):
+    if isinstance(v, str):
+        return v.strip().upper() in ('Y', 'YES', 'T', 'TRUE', '1')
+    return bool(v)
+
+
+def extraction_settings(sextractor_kws=None, header=None):
+    """Keyword arguments of ``Engine.extract`` from ``sextractor_kws`` and the image header (``SATURATE``)."""
+    kws = {str(k).upper(): v for k, v in (sextractor_kws or {}).items()}
+    for k in kws:
+        if k in _REFUSED or k.startswith(_REFUSED_PREFIXES):
+            raise ValueError(f'sextractor_kws: {k} would change a step this extractor does not have '
+                             f'(deblending, cleaning, mask correction and other filters are not in this version)')
+        if k not in _HONOURED and k not in _IGNORED:
+            raise ValueError(f'sextractor_kws: unknown key {k}')
+    thresh = float(kws.get('DETECT_THRESH', 1.5))
+    if 'ANALYSIS_THRESH' in kws and float(kws['ANALYSIS_THRESH']) != thresh:
+        raise ValueError('sextractor_kws: ANALYSIS_THRESH must equal DETECT_THRESH (measurements are isophotal at the '
+                         'detection threshold)')
+    if str(kws.get('WEIGHT_TYPE', 'MAP_WEIGHT')).upper() != 'MAP_WEIGHT':
+        raise ValueError('sextractor_kws: WEIGHT_TYPE must be MAP_WEIGHT')
+    aper = np.atleast_1d(kws.get('PHOT_APERTURES', 6.0)).astype(float)
+    if aper.size != 1:
+        raise ValueError('sextractor_kws: PHOT_APERTURES takes one diameter')
+    satur = kws.get('SATUR_LEVEL', (header or {}).get('SATURATE', 50000.0))
+    return dict(detect_thresh=thresh, detect_minarea=int(kws.get('DETECT_MINAREA', 5)), filter=_yes(kws.get('FILTER', 'Y')),
+                satur_level=float(satur), aper_radius=float(aper[0]) / 2.0)
 
 
 def prepare_sextractor(image, directory=None, checkimage_type=None,
@@ -29,9 +76,6 @@ def prepare_sextractor(image, directory=None, checkimage_type=None,
         if t not in checkimage_map:
             raise ValueError(f'Invalid CHECKIMAGE_TYPE "{t}". Must be one of '
                              f'{list(checkimage_map)}.')
-        if t not in _SUPPORTED:
-            raise NotImplementedError(f'CHECKIMAGE_TYPE "{t}" needs source extraction, '
-                                      f'which is outside the coadd / subtraction path')
     if use_weightmap:
         weight = image.weight_image.data
     else:
@@ -52,22 +96,57 @@ def prepare_sextractor(image, directory=None, checkimage_type=None,
                 outnames=outnames, types=checkimage_types)
 
 
+def _extract(image, call, sub, sextractor_kws):
+    """(PipelineFITSCatalog, segmentation map) of the background-subtracted plane ``sub``: noise = the image's
+    rms_image, bad = weight 0, flags = the mask."""
+    from .catalog import PipelineFITSCatalog
+    from .engine import get_engine
+    if call['catalog_type'] != 'FITS_LDAC':
+        raise ValueError(f'catalog_type "{call["catalog_type"]}": only FITS_LDAC catalogs are written')
+    settings = extraction_settings(sextractor_kws, image.header)
+    mask = getattr(image, 'mask_image', None)
+    try:
+        wcs = image.wcs
+    except (ValueError, KeyError, AttributeError):
+        wcs = None
+    tab, segm = get_engine().extract(sub, image.rms_image.data, bad=call['weight'] == 0,
+                                     flag=None if mask is None else mask.data, wcs=wcs, **settings)
+    cat = PipelineFITSCatalog()
+    base = image.local_path if image.ismapped else image.basename
+    cat.basename = os.path.basename(base).replace('.fits', '.cat')
+    cat.data = tab
+    cat.header = dict(image.header or {})
+    cat.header_comments = dict(image.header_comments or {})
+    if image.ismapped:
+        cat.map_to_local_file(base.replace('.fits', '.cat'))
+        cat.save()
+    return cat, segm
+
+
 def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir='/tmp',
-                   use_weightmap=True, sextractor_kws=None):
+                   use_weightmap=True, sextractor_kws=None, catalog=False):
     """Produce the requested check-images as FITSImage objects, written next to
     the image when it is mapped (``zuds/sextractor.py:110-150``).  The returned
-    list starts with ``None`` in the catalog slot."""
+    list starts with the catalog slot: ``None``, or with ``catalog=True`` (or when ``segm`` is among the
+    check-images) the ``PipelineFITSCatalog`` of the image."""
     from .engine import get_engine
     from .image import FITSImage
     call = prepare_sextractor(image, None, checkimage_type=checkimage_type,
                               catalog_type=catalog_type, use_weightmap=use_weightmap,
                               sextractor_kws=sextractor_kws)
+    call['catalog_type'] = catalog_type
+    extracting = bool(catalog) or any(t in _EXTRACTION for t in call['types'])
     want = {'bkg': 'bkg', 'rms': 'rms', 'bkgsub': 'sub'}
+    wanted = [want[t] for t in call['types'] if t in want]
+    if extracting and 'sub' not in wanted:
+        wanted.append('sub')
     bkg, rms, sub, stats = get_engine().background(
         image.data, call['weight'], mesh=call['mesh'], filtersize=call['filtersize'],
-        want=tuple(want[t] for t in call['types']))
+        want=tuple(wanted))
     planes = {'bkg': bkg, 'rms': rms, 'bkgsub': sub}
     result = [None]
+    if extracting:
+        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws)
     for t, name in zip(call['types'], call['outnames']):
         product = FITSImage()
         product.basename = os.path.basename(name)

@@ -551,6 +551,43 @@ int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
                int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
                int* out_status);
 
+/* ---- detection thumbnails: stamps of several planes on one grid --------------- */
+/* Replaces the thumbnail step of the subtraction driver (scripts/dosub.py:133-150 -> zuds/thumbnails.py:54-94,133-146):
+ * two whole-frame SWarp runs (sub.aligned_to(ref), sci.aligned_to(ref)) and a Cutout2D per detection and image, and the
+ * norms of make_triplet_for_braai (zuds/filterobjects.py:36-54).  Only the output tiles the stamps touch are resampled.
+ * The operator ("Detection thumbnails"):
+ *   origin   (x, y) = 0-based position of (ra, dec) on `wgrid`; the stamp covers x0 .. x0 + size - 1 with
+ *            x0 = ceil(x - size / 2), likewise y0 (the rule of astropy's overlap_slices / Cutout2D, restated);
+ *   pixels   of a plane on another grid: exactly the float32 zm_resample_dev(ctx, img, NULL, NULL, &plane.wcs, wgrid,
+ *            kernel, fscale, ...) writes to out_img at that grid pixel; of a plane with on_grid = 1: the plane's value,
+ *            untouched; 0 outside the grid (Cutout2D mode='partial', fill_value=0);
+ *   norm     L2 norm of the size x size block, squares summed in float64 in a fixed order (two runs: same bytes).
+ * kernel: ZM_RESAMPLE_LANCZOS3 or ZM_RESAMPLE_BILINEAR; default conventions only (zm_ctx_set_conventions). */
+#define ZM_STAMP_MAX 256            /* largest stamp size */
+#define ZM_STAMP_PLANES_MAX 8       /* planes per call */
+#define ZM_STAMP_NOT_FINITE 1       /* status of zm_stamp_origin: the position is not finite */
+#define ZM_STAMP_NO_OVERLAP 2       /* ... the stamp does not overlap the grid (Cutout2D: NoOverlapError) */
+typedef struct zm_stamp_plane {
+    const float* img;      /* [naxis2][naxis1] of `wcs`; device pointer for *_dev */
+    zm_wcs wcs;
+    double fscale;         /* as zm_resample; ignored when on_grid */
+    int32_t on_grid;       /* 1: plane is on the target grid already (gather) */
+    int32_t pad_;
+} zm_stamp_plane;
+/* host, float64: the origin rule; status[k] != 0 (ZM_STAMP_*): x0[k] / y0[k] are not to be used */
+int zm_stamp_origin(const zm_wcs* wgrid, int n, const double* ra, const double* dec,
+                    int size, int32_t* x0, int32_t* y0, int32_t* status);
+/* out [n][nplanes][size][size] float32, out_norm [n][nplanes] float64 (may be NULL): device memory; x0 / y0: host
+ * arrays.  Enqueued on the context's stream, nothing waited for.  n = 0: nothing happens.  A stamp that lies off the
+ * grid altogether is all 0. */
+int zm_stamps_dev(zm_ctx* ctx, int nplanes, const zm_stamp_plane* planes, const zm_wcs* wgrid,
+                  int kernel, int n, const int32_t* x0, const int32_t* y0, int size,
+                  float* out, double* out_norm);
+/* the same arguments on host planes and host outputs: planes are copied in, the call waits */
+int zm_stamps(zm_ctx* ctx, int nplanes, const zm_stamp_plane* planes, const zm_wcs* wgrid,
+              int kernel, int n, const int32_t* x0, const int32_t* y0, int size,
+              float* out, double* out_norm);
+
 /* ---- FITS data blocks on the device ------------------------------------------ */
 /* Replaces the host-side decode / encode astropy does inside FITSFile.load_data / save
  * (zuds/fitsfile.py:69-94,146-206): raw_dev holds the big-endian data block of a primary

@@ -2,12 +2,16 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits [--detect]
+usage: dosub.py images.txt ref.fits [--detect [--stamps]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
 With ``--detect`` every subtraction also gets its detection catalog (``sub.*.cat``, FITS_LDAC) and its filtered
 detections (``PipelineFITSCatalog.from_image`` -> ``Detection.from_catalog``, dosub.py:109-131).
+With ``--stamps`` (needs ``--detect``) every detection also gets its three thumbnails - difference, new and reference
+image on the reference image's grid (``Thumbnail.from_detections``, dosub.py:133-150) - and ``sub.*.stamps.fits`` is
+written next to the catalog: the zero-filled blocks ``[n, 3, 63, 63]`` (sub, new, ref) and a table with ``ra``, ``dec``,
+``x0``, ``y0`` and the shape of the stamp trimmed to the grid.
 """
 import os
 import sys
@@ -27,7 +31,28 @@ class PredecessorError(Exception):
     pass
 
 
-def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False):
+def write_stamps(sub, detections, stamps, size=None):
+    """``<sub>.stamps.fits``: primary array [n, 3, S, S] (the stamps of each detection, zero outside the grid) and one
+    row per detection."""
+    import numpy as np
+    size = size or zuds.CUTOUT_SIZE
+    n = len(detections)
+    blocks = np.zeros((n, 3, size, size), np.float32)
+    tab = np.zeros(n, dtype=[('ra', 'f8'), ('dec', 'f8'), ('x0', 'i4'), ('y0', 'i4'), ('nx_trim', 'i4'), ('ny_trim', 'i4')])
+    for k, d in enumerate(detections):
+        for p, s in enumerate(stamps[3 * k:3 * k + 3]):
+            a = np.flipud(s.array)                       # the stamp as stored: trimmed to the grid
+            ox, oy = max(s.x0, 0) - s.x0, max(s.y0, 0) - s.y0
+            blocks[k, p, oy:oy + a.shape[0], ox:ox + a.shape[1]] = a
+        s = stamps[3 * k]
+        tab[k] = (d.ra, d.dec, s.x0, s.y0, s.shape[1], s.shape[0])
+    out = sub.local_path.replace('.fits', '.stamps.fits')
+    zuds.fits.write_image_table(out, blocks, tab, {'STAMPSZ': size, 'NDET': n},
+                                {'STAMPSZ': 'stamp size in pixels', 'NDET': 'detections'})
+    return out
+
+
+def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -80,12 +105,22 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False):
         dstop = time.time()
         print(f'det: {dstop - dstart:.2f} sec to make detections for {sub.basename}', flush=True)
 
+    thumbs = None
+    if detect and stamps:
+        stampstart = time.time()
+        thumbs = zuds.Thumbnail.from_detections(detections, sub) if detections else []
+        write_stamps(sub, detections, thumbs)
+        stampstop = time.time()
+        print(f'stamp: {stampstop - stampstart:.2f} sec to make stamps for {sub.basename}', flush=True)
+
     cleanstart = time.time()
     sci.unmap()
     cleanstop = time.time()
     tstop = time.time()
     print(f'clean: took {cleanstop - cleanstart} sec to clean up after {sub.basename}"', flush=True)
     print(f'took {tstop - tstart} sec to make "{sub.basename}"', flush=True)
+    if detect and stamps:
+        return sub, detections, thumbs
     if detect:
         return sub, detections
     return sub
@@ -93,7 +128,11 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False):
 
 def main(argv):
     detect = '--detect' in argv
-    args = [a for a in argv if a != '--detect']
+    stamps = '--stamps' in argv
+    if stamps and not detect:
+        print('--stamps needs --detect', file=sys.stderr)
+        return 2
+    args = [a for a in argv if a not in ('--detect', '--stamps')]
     infile = args[0]
     refname = args[1]
     subclass = zuds.SingleEpochSubtraction
@@ -101,7 +140,7 @@ def main(argv):
     imgs = zuds.get_my_share_of_work(infile)
     for fn in imgs:
         try:
-            do_one(str(fn), sciclass, subclass, refname, detect=detect)
+            do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

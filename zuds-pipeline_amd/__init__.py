@@ -27,6 +27,7 @@ from .extract import *
 from .filterobjects import *
 from .catalog import *
 from .detections import *
+from .thumbnails import *
 from . import synth, fits
 
 # same DB-free entry points as the reference

@@ -111,6 +111,14 @@ class zm_object(C.Structure):
                 ('fluxerr_aper', C.c_double), ('x_world', C.c_double), ('y_world', C.c_double)]
 
 
+class zm_stamp_plane(C.Structure):
+    """One source plane of ``zm_stamps`` / ``zm_stamps_dev`` (include/zudsmi.h)."""
+    _fields_ = [('img', C.c_void_p), ('wcs', zm_wcs), ('fscale', C.c_double),
+                ('on_grid', C.c_int32), ('pad_', C.c_int32)]
+
+
+STAMP_MAX, STAMP_PLANES_MAX = 256, 8                   # ZM_STAMP_MAX, ZM_STAMP_PLANES_MAX
+STAMP_NOT_FINITE, STAMP_NO_OVERLAP = 1, 2              # zm_stamp_origin status words
 EXTRACT_CHAIN = 1                                      # zm_extract status bit (ZM_EXTRACT_CHAIN)
 HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4          # zm_hp_info.status bits (include/zudsmi.h)
 
@@ -217,6 +225,11 @@ _SIGS = {
                                  C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'zm_extract': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
                              C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'zm_stamp_origin': (C.c_int, [C.POINTER(zm_wcs), C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    'zm_stamps_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_stamp_plane), C.POINTER(zm_wcs), C.c_int, C.c_int, _P, _P,
+                                C.c_int, _P, _P]),
+    'zm_stamps': (C.c_int, [_P, C.c_int, C.POINTER(zm_stamp_plane), C.POINTER(zm_wcs), C.c_int, C.c_int, _P, _P,
+                            C.c_int, _P, _P]),
     'zm_timing_enable': (C.c_int, [_P, C.c_int]),
     'zm_timing_filter': (C.c_int, [_P, C.c_char_p]),
     'zm_timing_reset': (C.c_int, [_P]),

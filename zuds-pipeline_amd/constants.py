@@ -5,6 +5,7 @@ import numpy as np
 BIG_RMS = np.sqrt(50000.)          # zuds/constants.py:3
 BKG_BOX_SIZE = 128                 # zuds/constants.py:4
 MJD_TO_JD = 2400000.5
+CUTOUT_SIZE = 63                   # pix, zuds/constants.py:12
 APER_KEY = 'APCOR4'                # zuds/constants.py:13
 APERTURE_RADIUS = 3.0              # pixels, zuds/constants.py:14
 GROUP_PROPERTIES = ['field', 'ccdid', 'qid', 'fid']

@@ -72,6 +72,12 @@ static int ntaps_of(int kernel) {
     return kernel == ZM_RESAMPLE_LANCZOS3 ? 6 : kernel == ZM_RESAMPLE_BILINEAR ? 2 : 1;
 }
 
+// for the other translation units (stamps.hip): the checks and the LDS plan zm_resample_dev applies
+int zm_check_wcs(const zm_wcs* w, const char* what) { return check_wcs(w, what); }
+int zm_resample_lds_plan(const zm_map_params* mp, int onx, int ony, int kernel) {
+    return std::min(plan_lds(mp, onx, ony, ntaps_of(kernel)), 8000);
+}
+
 struct bk_plan {
     float* vs_all = nullptr;      // per frame: 4 floats, [0] = variance scale (RESCALE_WEIGHTS)
     int nslot = 1;                // meshes of the largest frame: the scratch slot of every frame

@@ -194,6 +194,8 @@ int zm_launch_coadd_fused(zm_ctx* ctx, const zm_ff* frames_host, int nfr, int ln
                           int32_t* out_mask, float* out_cov, int partial, int32_t* unmasked_out,
                           float2* stack = nullptr, int64_t fstride = 0, bool fits_own = false);
 int zm_get_lanczos_table(zm_ctx* ctx, const float** out);
+int zm_check_wcs(const zm_wcs* w, const char* what);                                   // api_coadd.hip
+int zm_resample_lds_plan(const zm_map_params* mp, int onx, int ony, int kernel);       // lds_elems of zm_resample_dev
 int zm_frame_background(zm_ctx* ctx, const float* img, const float* wgt, int nx, int ny,
                         int mesh, int fsize, float wthresh, int mode0, int nmode,
                         float** nodes_dev, float** stats_dev, int* nbx_out, int* nby_out,

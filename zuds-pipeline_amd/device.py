@@ -255,6 +255,22 @@ class DeviceSubtraction(object):
                                                   wcs=self.wsci if wcs is None else wcs, segm=segm.data_ptr(), **kw)
         return tab, nfound, segm
 
+    def stamps(self, ra, dec, sci, ref, size=63, ref_flxscale=1.0, sci_flxscale=1.0, kernel='LANCZOS3'):
+        """The thumbnails of the resident difference image (``Engine.stamps``; scripts/dosub.py:133-150): per position
+        the stamps of ``self.diff`` and ``sci`` (science grid, resampled onto the reference grid under the stamps only)
+        and of the un-aligned ``ref`` (gathered) - the tensors the caller handed to ``run``, which this object does not
+        keep.  Enqueued on this chain's stream behind the subtraction; only blocks and norms cross PCIe.
+        ``sci_flxscale``: the FLXSCALE card of the science frame and of the difference image (``swarp.run_align``);
+        ``ref_flxscale`` is accepted for symmetry with ``run`` (a gathered plane is not scaled).
+        Returns (blocks[n, 3, S, S] in the order sub, new, ref, norms[n, 3], x0, y0)."""
+        self.result()
+        fs = self.engine.flux_scale(self.wsci, self.wref, float(sci_flxscale))
+        self.engine.set_stream(self.stream.cuda_stream)
+        self.stream.wait_stream(self.torch.cuda.current_stream(self.device))
+        planes = [dict(img=self.diff, wcs=self.wsci, fscale=fs), dict(img=sci.contiguous(), wcs=self.wsci, fscale=fs),
+                  dict(img=ref.contiguous(), wcs=self.wref, on_grid=True)]
+        return self.engine.stamps(planes, self.wref, ra, dec, size=size, kernel=kernel, stream=self.stream)
+
     def release_overlap(self):
         """Give the second context of ``overlap=True`` back (it is made again on the next run that wants it)."""
         if self._bk_engine is not None:

@@ -393,3 +393,4 @@ def hp_params(**kw):
 
 
 from . import extract as _extract  # noqa: E402,F401  (Engine.extract / Engine.extract_dev)
+from . import thumbnails as _thumbnails  # noqa: E402,F401  (Engine.stamps)

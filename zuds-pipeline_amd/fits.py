@@ -235,6 +235,12 @@ def _card(key, value, comment=''):
 def write(path, data, header=None, comments=None):
     """Write a primary-HDU image (overwrites).  ``header`` values that describe
     the array (SIMPLE / BITPIX / NAXIS* / BSCALE / BZERO) are regenerated."""
+    with open(path, 'wb') as f:
+        f.write(to_bytes(data, header, comments))
+
+
+def to_bytes(data, header=None, comments=None, cards=()):
+    """The bytes ``write`` puts into the file (a thumbnail's FITS file never touches a disk, zuds/thumbnails.py:84-91)."""
     header = dict(header or {})
     comments = comments or {}
     data = np.asarray(data)
@@ -265,12 +271,98 @@ def write(path, data, header=None, comments=None):
         data = data.astype(np.int16)
     else:
         raise ValueError(f'cannot write dtype {kind} to FITS')
-    hdr = header_block(data.shape, bitpix, header, comments, extra)
+    hdr = header_block(data.shape, bitpix, header, comments, list(cards) + list(extra))
     raw = np.ascontiguousarray(data).astype(np.dtype(_BITPIX_DTYPE[bitpix])).tobytes()
+    return hdr + raw + b'\0' * (-len(raw) % BLOCK)
+
+
+def _decode(raw, header, what):
+    """Physical values of the data block ``raw`` (big-endian array of the header's shape)."""
+    bitpix = int(header['BITPIX'])
+    dt = np.dtype(_BITPIX_DTYPE[bitpix])
+    data = raw.astype(dt.newbyteorder('='))
+    bscale = header.get('BSCALE', 1)
+    bzero = header.get('BZERO', 0)
+    if bscale != 1 or bzero != 0:
+        if bscale == 1 and float(bzero).is_integer() and bitpix > 0:
+            unsigned = {16: (32768, np.uint16), 32: (2147483648, np.uint32)}
+            if bitpix in unsigned and int(bzero) == unsigned[bitpix][0]:
+                data = (data.astype(np.int64) + int(bzero)).astype(unsigned[bitpix][1])
+            else:
+                data = data.astype(np.int64) + int(bzero)
+        else:
+            data = (data * np.float64(bscale) + np.float64(bzero)).astype(np.float32)
+    return data
+
+
+def from_bytes(buf):
+    """``read`` on the bytes of a FITS file held in memory: (data or None, header dict, comments dict)."""
+    import io
+    buf = bytes(buf)
+    header, comments, off = _read_header(io.BytesIO(buf).read, 'FITS bytes')
+    naxis = int(header.get('NAXIS', 0))
+    if naxis == 0:
+        return None, header, comments
+    shape = tuple(int(header[f'NAXIS{i}']) for i in range(naxis, 0, -1))
+    bitpix = int(header['BITPIX'])
+    if bitpix not in _BITPIX_DTYPE:
+        raise ValueError(f'FITS bytes: unsupported BITPIX {bitpix}')
+    count = int(np.prod(shape))
+    dt = np.dtype(_BITPIX_DTYPE[bitpix])
+    if len(buf) < off + count * dt.itemsize:
+        raise ValueError(f'FITS bytes: truncated data ({len(buf) - off} of {count * dt.itemsize} bytes)')
+    raw = np.frombuffer(buf, dtype=dt, count=count, offset=off).reshape(shape)
+    return _decode(raw, header, 'FITS bytes'), header, comments
+
+
+def write_image_table(path, data, table, header=None, comments=None, extname='STAMPS', extra=()):
+    """A primary-HDU image followed by ONE binary table of scalar columns (the columns ``write_ldac`` takes): the
+    stamps file of scripts/dosub.py --stamps."""
+    table = np.asarray(table)
+    names = table.dtype.names
+    cols, fields = [], []
+    for i, name in enumerate(names, 1):
+        dt = table.dtype[name]
+        code = 'u1' if dt.kind == 'b' else dt.kind + str(dt.itemsize)
+        if dt.shape or code not in _TFORM:
+            raise ValueError(f'column {name}: dtype {dt} has no FITS binary-table column type here')
+        fields.append((name, '>' + code))
+        cols += [_card(f'TTYPE{i}', name), _card(f'TFORM{i}', '1' + _TFORM[code])]
+    big = np.empty(len(table), dtype=fields)
+    for name in names:
+        big[name] = table[name]
+    head = to_bytes(data, header, comments, cards=[('EXTEND', True, 'a binary table follows')])
     with open(path, 'wb') as f:
-        f.write(hdr)
-        f.write(raw)
-        f.write(b'\0' * (-len(raw) % BLOCK))
+        f.write(head)
+        f.write(_table_hdu(extname, [_card('TFIELDS', len(names))] + cols, big.dtype.itemsize, len(table),
+                           big.tobytes(), extra))
+
+
+def read_image_table(path):
+    """(data, header, table as a native-endian record array, table header) of a file ``write_image_table`` wrote."""
+    data, header, _ = read(path)
+    _, _, off = read_header(path)
+    nbytes = 0 if data is None else int(np.prod(data.shape)) * abs(int(header['BITPIX'])) // 8
+    with open(path, 'rb') as f:
+        f.seek(off + nbytes + (-nbytes % BLOCK))
+        h, _, _ = _read_header(f.read, path, primary=False)
+        if h.get('XTENSION') != 'BINTABLE':
+            raise ValueError(f'{path}: expected a binary table behind the image')
+        fields = []
+        for i in range(1, int(h['TFIELDS']) + 1):
+            code = str(h[f'TFORM{i}']).strip().lstrip('1')
+            if code not in _TFORM_DTYPE:
+                raise ValueError(f'{path}: column {h[f"TTYPE{i}"]}: only scalar B I J K E D columns')
+            fields.append((str(h[f'TTYPE{i}']).strip(), _TFORM_DTYPE[code]))
+        n = int(h['NAXIS1']) * int(h['NAXIS2'])
+        body = f.read(n)
+        if len(body) != n:
+            raise ValueError(f'{path}: truncated table')
+    big = np.frombuffer(body, dtype=fields, count=int(h['NAXIS2']))
+    native = np.empty(len(big), dtype=[(nm, np.dtype(t).newbyteorder('=')) for nm, t in fields])
+    for nm, _ in fields:
+        native[nm] = big[nm]
+    return data, header, native.view(np.recarray), h
 
 
 # ---- FITS_LDAC ------------------------------------------------------------------------------------------------

@@ -8,7 +8,10 @@ the exact fraction of each pixel inside the circle; ``flags`` = bitwise OR of th
 mask over the aperture's bounding box (``to_mask(method='center').cutout(mask)``
 returns the raw cutout, not the circle).  photutils itself is absent here; the
 exact circle / pixel overlap below is the closed-form area (quarter-box
-decomposition), pinned by analytic tests (sum of fractions = pi r^2).
+decomposition).  It is pinned by ``tests/test_aperture_ref.py``: every ring pixel of nine radii against
+``tests/aperture_ref.py``, a quadrature that shares no formula with it and is itself held to 50-digit arithmetic;
+the HIP kernel is held to the same reference in ``tests/test_photometry_gpu.py``.  A pixel that is not finite
+makes the sum it enters non-finite wherever in the box it lies; a position that is not finite has no aperture.
 """
 import numpy as np
 
@@ -55,6 +58,8 @@ def aperture_photometry(data, rms, mask, x, y, r=3.0):
     err = np.zeros(len(x))
     flags = np.zeros(len(x), dtype=np.int64)
     for k, (xc, yc) in enumerate(zip(x, y)):
+        if not (np.isfinite(xc) and np.isfinite(yc)):      # no aperture: zeros, as for one that misses the frame
+            continue
         ixmin, ixmax, iymin, iymax = bbox(xc, yc, r)
         i0, i1 = max(ixmin, 0), min(ixmax, nx)
         j0, j1 = max(iymin, 0), min(iymax, ny)
@@ -62,8 +67,13 @@ def aperture_photometry(data, rms, mask, x, y, r=3.0):
             continue
         jj, ii = np.mgrid[j0:j1, i0:i1]
         frac = overlap_fraction(ii - 0.5 - xc, ii + 0.5 - xc, jj - 0.5 - yc, jj + 0.5 - yc, r)
-        flux[k] = (data[j0:j1, i0:i1] * frac).sum()
-        err[k] = np.sqrt((rms[j0:j1, i0:i1] ** 2 * frac).sum())
+        with np.errstate(invalid='ignore', over='ignore'):
+            flux[k] = (data[j0:j1, i0:i1] * frac).sum()
+        # (the closed form leaves fractions of -1e-15 on pixels outside the circle: a finite sum that rounds below 0
+        # is 0; one that is not finite stays so, and its error is NaN or inf)
+        with np.errstate(invalid='ignore', over='ignore'):
+            v = (rms[j0:j1, i0:i1] ** 2 * frac).sum()
+            err[k] = np.sqrt(max(v, 0.0) if np.isfinite(v) else v)
         if mask is not None:
             flags[k] = int(np.bitwise_or.reduce(np.asarray(mask)[j0:j1, i0:i1].astype(np.int64), axis=(0, 1)))
     return flux, err, flags

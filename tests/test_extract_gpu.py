@@ -122,6 +122,25 @@ def test_star_fields_with_every_kind_of_bad_pixel(engine, shape):
             assert (tab['FLAGS'] & 4).any()
 
 
+def test_aperture_columns_against_the_independent_reference(engine):
+    """FLUX_APER / FLUXERR_APER directly against tests/aperture_ref.py (a quadrature that shares no formula with the
+    kernel or with the oracle that extract_ref takes its fractions from), on the same planes at the catalog's radius
+    and barycentres, within that reference's own bound: sum |img| * (fraction limit) + n eps sum |img * frac|."""
+    import aperture_ref as ar
+    img, sigma, bad, flag = field(400, 360, seed=77, poison=False)
+    for rad in (3.0, 4.5):
+        t = engine.extract(img, sigma, bad, flag, full=True, aper_radius=rad)['table']
+        keep = np.flatnonzero((t['FLAGS'] & (8 | 16)) == 0)                  # away from the border: whole apertures
+        assert keep.size >= 8
+        x, y = t['X_IMAGE'][keep] - 1.0, t['Y_IMAGE'][keep] - 1.0
+        f, e, _, terms = ar.aperture_sums(img, sigma, None, x, y, rad, with_terms=True)
+        bf, bv = ar.sums_bounds(terms)
+        df, dv = np.abs(t['FLUX_APER'][keep] - f), np.abs(t['FLUXERR_APER'][keep] ** 2 - e ** 2)
+        print(f'extract aperture columns against aperture_ref, r = {rad}: {keep.size} objects; worst flux {df.max():.3g} '
+              f'(ratio to bound {np.max(df / bf):.3g}), worst variance {dv.max():.3g} (ratio {np.max(dv / bv):.3g})')
+        assert (f > 0).all() and (df <= bf).all() and (dv <= bv).all()
+
+
 def test_one_by_one_frames(engine):
     one = np.full((1, 1), 10.0, np.float32)
     for minarea, n in ((1, 1), (5, 0)):

@@ -37,15 +37,19 @@ __global__ __launch_bounds__(64) void k_aperture(const float* __restrict__ img,
     const int k = blockIdx.x, lane = threadIdx.x;
     if (k >= npos) return;
     const double xc = xs[k], yc = ys[k];
-    // photutils BoundingBox.from_float(x - r, x + r, y - r, y + r)
-    int ixmin = (int)floor(xc - r + 0.5), ixmax = (int)ceil(xc + r + 0.5);
-    int iymin = (int)floor(yc - r + 0.5), iymax = (int)ceil(yc + r + 0.5);
-    ixmin = max(ixmin, 0); ixmax = min(ixmax, nx);
-    iymin = max(iymin, 0); iymax = min(iymax, ny);
+    int ixmin = 0, ixmax = 0, iymin = 0, iymax = 0;
+    if (isfinite(xc) && isfinite(yc)) {
+        // photutils BoundingBox.from_float(x - r, x + r, y - r, y + r), clipped to the frame.  The bounds are
+        // clamped to [-1, n + 1] while still double: a double outside int's range has no defined conversion
+        ixmin = max((int)fmin(fmax(floor(xc - r + 0.5), -1.0), nx + 1.0), 0);
+        ixmax = min((int)fmin(fmax(ceil(xc + r + 0.5), -1.0), nx + 1.0), nx);
+        iymin = max((int)fmin(fmax(floor(yc - r + 0.5), -1.0), ny + 1.0), 0);
+        iymax = min((int)fmin(fmax(ceil(yc + r + 0.5), -1.0), ny + 1.0), ny);
+    }
     const int bw = ixmax - ixmin, bh = iymax - iymin;
     double f = 0.0, v = 0.0;
     int fl = 0;
-    if (bw > 0 && bh > 0 && isfinite(xc) && isfinite(yc)) {
+    if (bw > 0 && bh > 0) {
         for (int e = lane; e < bw * bh; e += 64) {
             const int j = iymin + e / bw, i = ixmin + e % bw;
             const double x0 = i - 0.5 - xc, x1 = i + 0.5 - xc, y0 = j - 0.5 - yc, y1 = j + 0.5 - yc;
@@ -65,7 +69,9 @@ __global__ __launch_bounds__(64) void k_aperture(const float* __restrict__ img,
     }
     if (lane == 0) {
         flux[k] = f;
-        err[k] = sqrt(fmax(v, 0.0));
+        // a finite sum that rounds below 0 is 0; one that is not finite stays so (fmax alone would turn a NaN
+        // variance into an error of 0)
+        err[k] = sqrt(isfinite(v) ? fmax(v, 0.0) : v);
         flags[k] = fl;
     }
 }

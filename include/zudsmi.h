@@ -490,6 +490,17 @@ int zm_find_stars_dev(zm_ctx* ctx, const float* img, const uint8_t* bad, int nx,
 int zm_star_fwhm_dev(zm_ctx* ctx, const float* img, int nx, int ny, int nstar,
                      const int* x, const int* y, int half, double* out_fwhm,
                      double* out_cx, double* out_cy);
+/* The three pixel cuts of filter_sexcat (zuds/filterobjects.py:83-195) on planes that are already in HBM (d_img,
+ * d_rms, d_mask: device pointers; everything else: host arrays).  x, y: X_IMAGE / Y_IMAGE, 1-based, handed to the
+ * r = 6 aperture unchanged as the reference does.  Per candidate: out_bpmcut = exact-overlap aperture sum of
+ * (mask & bad_bits) != 0, out_rmscut = aperture sum of d_rms / (pi 36), out_negpix = the dipole test of
+ * zm_negpix_test.  out_stats = {medcut, immed, imsig}: 1.1 x the median of d_rms over (mask & bad_bits) == 0, the
+ * median of d_img over all pixels, 1.48 x its MAD; taken on the device and read by the cuts from device memory.
+ * A position that is not finite gives zero sums and negpix 0.  npos == 0 returns at once and writes nothing.
+ * Fails when no pixel is good or the image has no spread (imsig = 0). */
+int zm_candidate_cuts_dev(zm_ctx* ctx, const float* d_img, const float* d_rms, const int32_t* d_mask,
+                          int32_t bad_bits, int nx, int ny, int npos, const double* x, const double* y,
+                          double* out_bpmcut, double* out_rmscut, int32_t* out_negpix, double* out_stats);
 
 /* ---- source extraction: detection catalog and segmentation map -------------- */
 /* Replaces the SExtractor run of PipelineFITSCatalog.from_image (zuds/catalog.py:96-130) with the

@@ -6,6 +6,7 @@ subtractions as one batch of launches on each of J lanes (``nightly.SubtractionP
 ``--fit-batch 0``: J separate subtractions in flight).
 
 usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch B] [--batch FRAMES] [--nreg-side N]
+                    [--detect [--stamps]]
 
 * ``images.txt``: science image paths (``*sciimg.fits``; the mask is ``*mskimg.fits``; a
   ``.weight.fits`` sibling is required: 1 / rms^2, 0 on bad pixels).  The list is sharded over
@@ -17,7 +18,13 @@ usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch 
 
 Products per image, with the reference's names: ``sub.<sci>_<ref>.fits``, ``.rms.fits``,
 ``.mask.fits`` next to the science image.  An image whose subtraction exists is skipped
-(the reference's checkpoint by name, ``scripts/dosub.py:85-94``)."""
+(the reference's checkpoint by name, ``scripts/dosub.py:85-94``).
+
+``--detect``: every subtraction also gets its filtered detection catalog ``sub.*.cat`` (FITS_LDAC, the file of
+``dosub.py --detect``: what ``dosub.do_one`` hands back to the reference's night), made on the planes in HBM
+(``DeviceSubtraction.candidates``).  ``--stamps`` (needs ``--detect``): and ``sub.*.stamps.fits``, the thumbnails of
+its ``GOODCUT == 1`` rows in the layout of ``dosub.py --stamps``; more than 50 such rows: no stamps file (the
+reference's TooManyDetectionsError)."""
 import argparse
 import importlib
 import os
@@ -76,7 +83,7 @@ def finish_science(io, fn, img, hdr, mask, wgt):
         if 'SATURATE' in hdr:         # zuds/image.py:203-204
             rms = torch.where(img >= 0.9 * float(hdr['SATURATE']), torch.full_like(rms, float(zuds.BIG_RMS)), rms)
     return dict(img=img, rms=rms, mask=mask, wgt=wgt, wcs=zuds.WCS.from_header(hdr),
-                seeing=float(hdr['SEEING']), header=hdr, path=fn)
+                seeing=float(hdr['SEEING']), flxscale=float(hdr.get('FLXSCALE', 1.0)), header=hdr, path=fn)
 
 
 def load_science(io, fn):
@@ -85,6 +92,48 @@ def load_science(io, fn):
     sci = finish_science(io, fn, img, hdr, mask, wgt)
     io.stream.synchronize()
     return sci
+
+
+def _load_dosub():
+    """scripts/dosub.py as a module: it owns the layout of the stamps file and the guard MAX_DETS."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('dosub', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'dosub.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+dosub = _load_dosub()
+MAX_DETS = dosub.MAX_DETS         # more detections than this on one subtraction and it gets no stamps
+
+
+def write_detections(out, hdr, ref, res):
+    """``sub.*.cat`` and ``sub.*.stamps.fits`` of one result (``SubtractionJob(detect=True, stamps=...)``)."""
+    name = os.path.basename(out)
+    if res.get('cat') is None:
+        print(f'{name}: no detections: {res.get("detect_error")}', flush=True)
+        return
+    cat = zuds.PipelineFITSCatalog()
+    cat.basename = name.replace('.fits', '.cat')
+    cat.map_to_local_file(out.replace('.fits', '.cat'))
+    cat.data, cat.header, cat.header_comments = res['cat'], dict(hdr), {}
+    cat.save()
+    if res.get('too_many'):
+        print(f'Error: {int((res["cat"]["GOODCUT"] == 1).sum())} detections (>{MAX_DETS}) '
+              f'on "{name}", something wrong with the image probably', flush=True)
+    elif 'stamps_error' in res:
+        print(f'{name}: no stamps: {res["stamps_error"]}', flush=True)
+    elif 'stamps' in res:
+        st = res['stamps']
+        thumbs = importlib.import_module('zuds-pipeline_amd.thumbnails')
+        gnx, gny = (int(v) for v in ref['wcs'].naxis)
+        size = st['blocks'].shape[-1]
+        trimmed = []
+        for x0, y0 in zip(st['x0'], st['y0']):
+            (sy, sx), _ = thumbs.trim_slices(int(x0), int(y0), size, gnx, gny)
+            trimmed.append((sx.stop - sx.start, sy.stop - sy.start))
+        dosub.write_stamp_blocks(out.replace('.fits', '.stamps.fits'), st['blocks'], st['ra'], st['dec'], st['x0'],
+                                    st['y0'], trimmed)
 
 
 def write_products(io, sci, ref, res):
@@ -111,6 +160,8 @@ def write_products(io, sci, ref, res):
                    [zp] * ra.size, [jd] * ra.size)
         with open(out.replace('.fits', '.phot.txt'), 'w') as fh:
             fh.write('# ra dec flux fluxerr flags zp obsjd\n' + ''.join([fmt % r for r in rows]))
+    if 'cat' in res:
+        write_detections(out, hdr, ref, res)
     return out
 
 
@@ -129,7 +180,12 @@ def main(argv=None):
                          'as one batch, zm_subtract_batch_dev; measured on 32 subtractions of 3072^2: three lanes of '
                          '11 = 2.0 - 2.1 ms each whether the frames share one seeing or fall into three seeing '
                          'groups, two lanes of 16 1.95 / 2.8, 8 - 16 separate chains 3.0); 0: one chain per job')
+    ap.add_argument('--detect', action='store_true', help='write the filtered detection catalog sub.*.cat of every subtraction')
+    ap.add_argument('--stamps', action='store_true', help='with --detect: write sub.*.stamps.fits, the thumbnails of the detections')
     args = ap.parse_args(argv)
+    if args.stamps and not args.detect:
+        print('--stamps needs --detect', file=sys.stderr)
+        return 2
 
     nightly = importlib.import_module('zuds-pipeline_amd.nightly')
     device = importlib.import_module('zuds-pipeline_amd.device')
@@ -148,13 +204,14 @@ def main(argv=None):
     pool = nightly.SubtractionPool(args.jobs, device=local, batch=args.fit_batch)
     ring = importlib.import_module('zuds-pipeline_amd.fitsring').FITSRing(local)
     try:
-        return run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side)
+        return run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side,
+                         detect=args.detect, stamps=args.stamps)
     finally:
         pool.close()
         ring.close()
 
 
-def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3):
+def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False):
     """The images of this rank against one reference.  The files of batch b + 1 are read, sent and decoded by the
     ring (fitsring.FITSRing: reader threads, copy stream) while the pool subtracts batch b; the products of batch b
     are encoded on the device, copied back on a third stream and written by the ring's writer threads while
@@ -213,7 +270,8 @@ def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3):
                 continue
             sci['radec'] = radec
             scis.append(sci)
-            jobs.append(nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn))
+            jobs.append(nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
+                                               stamps=stamps, max_detections=MAX_DETS))
         io.stream.synchronize()                  # (the rms maps; the pool's lanes read them on their own streams)
         return scis, jobs, (1e3 * (t1 - t0), 1e3 * (time.time() - t1))
     finisher = ThreadPoolExecutor(1, thread_name_prefix='zmnight-fin')

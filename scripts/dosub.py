@@ -31,6 +31,19 @@ class PredecessorError(Exception):
     pass
 
 
+def write_stamp_blocks(out, blocks, ra, dec, x0, y0, trimmed):
+    """The stamps file: primary array ``blocks`` [n, 3, S, S] (sub, new, ref; zero outside the grid) and one row per
+    detection: ``ra``, ``dec``, ``x0``, ``y0`` and ``trimmed`` = (nx, ny) of the stamp trimmed to the grid."""
+    import numpy as np
+    n, size = len(blocks), blocks.shape[-1]
+    tab = np.zeros(n, dtype=[('ra', 'f8'), ('dec', 'f8'), ('x0', 'i4'), ('y0', 'i4'), ('nx_trim', 'i4'), ('ny_trim', 'i4')])
+    for k in range(n):
+        tab[k] = (ra[k], dec[k], x0[k], y0[k], trimmed[k][0], trimmed[k][1])
+    zuds.fits.write_image_table(out, blocks, tab, {'STAMPSZ': size, 'NDET': n},
+                                {'STAMPSZ': 'stamp size in pixels', 'NDET': 'detections'})
+    return out
+
+
 def write_stamps(sub, detections, stamps, size=None):
     """``<sub>.stamps.fits``: primary array [n, 3, S, S] (the stamps of each detection, zero outside the grid) and one
     row per detection."""
@@ -38,18 +51,18 @@ def write_stamps(sub, detections, stamps, size=None):
     size = size or zuds.CUTOUT_SIZE
     n = len(detections)
     blocks = np.zeros((n, 3, size, size), np.float32)
-    tab = np.zeros(n, dtype=[('ra', 'f8'), ('dec', 'f8'), ('x0', 'i4'), ('y0', 'i4'), ('nx_trim', 'i4'), ('ny_trim', 'i4')])
+    x0, y0, trimmed = [], [], []
     for k, d in enumerate(detections):
         for p, s in enumerate(stamps[3 * k:3 * k + 3]):
             a = np.flipud(s.array)                       # the stamp as stored: trimmed to the grid
             ox, oy = max(s.x0, 0) - s.x0, max(s.y0, 0) - s.y0
             blocks[k, p, oy:oy + a.shape[0], ox:ox + a.shape[1]] = a
         s = stamps[3 * k]
-        tab[k] = (d.ra, d.dec, s.x0, s.y0, s.shape[1], s.shape[0])
-    out = sub.local_path.replace('.fits', '.stamps.fits')
-    zuds.fits.write_image_table(out, blocks, tab, {'STAMPSZ': size, 'NDET': n},
-                                {'STAMPSZ': 'stamp size in pixels', 'NDET': 'detections'})
-    return out
+        x0.append(s.x0)
+        y0.append(s.y0)
+        trimmed.append((s.shape[1], s.shape[0]))
+    return write_stamp_blocks(sub.local_path.replace('.fits', '.stamps.fits'), blocks, [d.ra for d in detections],
+                              [d.dec for d in detections], x0, y0, trimmed)
 
 
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False):

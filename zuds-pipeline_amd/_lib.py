@@ -196,6 +196,7 @@ _SIGS = {
                                     C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
     'zm_star_fwhm_dev': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     'zm_negpix_test': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P]),
+    'zm_candidate_cuts_dev': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     'zm_fits_decode_dev': (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_int, _P]),
     'zm_fits_encode_dev': (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     'zm_mask_accum_dev': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int]),

@@ -10,8 +10,13 @@
 //   zm_negpix_test   the "negative pixel next to a positive one" dipole cut of
 //                    filter_sexcat (zuds/filterobjects.py:155-195)
 //
+//   zm_candidate_cuts_dev   the three pixel cuts of filter_sexcat (BPMCUT, RMSCUT against MEDCUT, the dipole
+//                    cut) on planes that are already in HBM, frame statistics included, one wave per candidate
+//
 // Conventions (chosen, stated in oracle/detect.py): see there.
-#include "zm_internal.h"
+#include <algorithm>
+
+#include "aperture_dev.h"
 
 // out: candidates in no particular order (the host sorts by peak value, then y, then x)
 __global__ __launch_bounds__(256) void k_find_stars(const float* __restrict__ img,
@@ -111,6 +116,142 @@ __global__ void k_negpix(const float* __restrict__ img, int nx, int ny, int npos
                 }
         }
     bad[k] = b;
+}
+
+// ---- the three pixel cuts of filter_sexcat on resident planes, one wave per candidate -------------------------
+// out = mask & bits: the select counts a pixel whose mask word is 0, the cuts count one without a bad bit
+__global__ __launch_bounds__(256) void k_cc_mask(const int32_t* __restrict__ mask, int32_t bits, int64_t n,
+                                                 int32_t* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) out[p] = mask[p] & bits;
+}
+
+#define CC_RADIUS 6.0        // zuds/filterobjects.py:102-104
+#define CC_HALF 5            // CUTSIZE 11, zuds/filterobjects.py:12
+
+// sel: the six doubles of zm_median_mad2_async_dev, {median, sigma, count} of the rms plane over the good pixels and
+// of the image.  xs, ys: X_IMAGE / Y_IMAGE as SExtractor reports them (1-based), handed to the aperture unchanged
+// as the reference hands them to photutils; the dipole test subtracts the 1 as the reference does.
+// Lanes walk the bounding box of the aperture as k_aperture does (element e to lane e mod 64, float64 partials,
+// xor-shuffle reduction); the overlap of a pixel is taken once and weighs both planes.
+__global__ __launch_bounds__(64) void k_candidate_cuts(const float* __restrict__ img, const float* __restrict__ rms,
+                                                       const int32_t* __restrict__ mask, int32_t bad_bits, int nx,
+                                                       int ny, int npos, const double* __restrict__ xs,
+                                                       const double* __restrict__ ys, const double* __restrict__ sel,
+                                                       double* __restrict__ bpmcut, double* __restrict__ rmscut,
+                                                       int32_t* __restrict__ negpix, double* __restrict__ stats) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (k >= npos) return;
+    const double medcut = 1.1 * sel[0];
+    const double immed = sel[3];
+    const double imsig = 1.48 * (sel[4] / 1.4826);
+    if (k == 0 && lane == 0) {
+        stats[0] = medcut; stats[1] = immed; stats[2] = imsig;
+        stats[3] = sel[2]; stats[4] = sel[5];               // the two sample counts: the host refuses an empty frame
+    }
+    const double xc = xs[k], yc = ys[k], r = CC_RADIUS;
+    const bool fin = isfinite(xc) && isfinite(yc);
+    int ixmin = 0, ixmax = 0, iymin = 0, iymax = 0;
+    if (fin) {
+        // (k_aperture: clamped while still double)
+        ixmin = max((int)fmin(fmax(floor(xc - r + 0.5), -1.0), nx + 1.0), 0);
+        ixmax = min((int)fmin(fmax(ceil(xc + r + 0.5), -1.0), nx + 1.0), nx);
+        iymin = max((int)fmin(fmax(floor(yc - r + 0.5), -1.0), ny + 1.0), 0);
+        iymax = min((int)fmin(fmax(ceil(yc + r + 0.5), -1.0), ny + 1.0), ny);
+    }
+    const int bw = ixmax - ixmin, bh = iymax - iymin;
+    double sr = 0.0, sb = 0.0;
+    if (bw > 0 && bh > 0) {
+        for (int e = lane; e < bw * bh; e += 64) {
+            const int j = iymin + e / bw, i = ixmin + e % bw;
+            const double x0 = i - 0.5 - xc, x1 = i + 0.5 - xc, y0 = j - 0.5 - yc, y1 = j + 0.5 - yc;
+            const double frac = ap_signed(x1, y1, r) - ap_signed(x0, y1, r) - ap_signed(x1, y0, r) +
+                                ap_signed(x0, y0, r);
+            const size_t idx = (size_t)j * nx + i;
+            sr += (double)rms[idx] * frac;
+            if (mask[idx] & bad_bits) sb += frac;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        sr += __shfl_xor(sr, o);
+        sb += __shfl_xor(sb, o);
+    }
+    // the dipole test (k_negpix's rule): lanes take the pixels of the 11 x 11 cutout, each looks at its 3 x 3
+    // neighbours inside the 13 x 13 cutout and the frame.  The centre is clamped while still double: further than
+    // 64 pixels outside the frame no cutout pixel is inside it, wherever the centre lies.
+    bool hit = false;
+    if (fin) {
+        const int cx = (int)fmin(fmax(rint(xc), -64.0), nx + 64.0) - 1;     // np.round: half to even
+        const int cy = (int)fmin(fmax(rint(yc), -64.0), ny + 64.0) - 1;
+        const float med = (float)immed, sig = (float)imsig;
+        const int side = 2 * CC_HALF + 1;
+        for (int e = lane; e < side * side; e += 64) {
+            const int j = cy - CC_HALF + e / side, i = cx - CC_HALF + e % side;
+            if (i < 0 || i >= nx || j < 0 || j >= ny) continue;
+            if (!((img[(size_t)j * nx + i] - med) / sig < -5.f)) continue;
+            for (int dj = -1; dj <= 1; ++dj)
+                for (int di = -1; di <= 1; ++di) {
+                    const int ii = i + di, jj = j + dj;
+                    if (ii < cx - CC_HALF - 1 || ii > cx + CC_HALF + 1 || jj < cy - CC_HALF - 1 || jj > cy + CC_HALF + 1) continue;
+                    if (ii < 0 || ii >= nx || jj < 0 || jj >= ny) continue;
+                    if ((img[(size_t)jj * nx + ii] - med) / sig > 5.f) hit = true;
+                }
+        }
+    }
+    const bool any = __ballot(hit) != 0ull;
+    if (lane == 0) {
+        bpmcut[k] = sb;
+        rmscut[k] = sr / (M_PI * CC_RADIUS * CC_RADIUS);
+        negpix[k] = any ? 1 : 0;
+    }
+}
+
+// img / rms / mask: device planes.  Positions in, cuts and the three frame statistics out: host arrays, one copy.
+extern "C" int zm_candidate_cuts_dev(zm_ctx* ctx, const float* d_img, const float* d_rms, const int32_t* d_mask,
+                                     int32_t bad_bits, int nx, int ny, int npos, const double* x, const double* y,
+                                     double* out_bpmcut, double* out_rmscut, int32_t* out_negpix, double* out_stats) {
+    ZM_CHECK(ctx && d_img && d_rms && d_mask, "zm_candidate_cuts_dev: null plane");
+    ZM_CHECK(nx > 0 && ny > 0 && npos >= 0, "zm_candidate_cuts_dev: bad sizes");
+    if (npos == 0) return 0;
+    ZM_CHECK(x && y && out_bpmcut && out_rmscut && out_negpix && out_stats, "zm_candidate_cuts_dev: null argument");
+    ZM_HIP(hipSetDevice(ctx->device));
+    const int64_t np = (int64_t)nx * ny;
+    int32_t* d_good = nullptr;
+    double* d_buf = nullptr;
+    ZM_TRY(ctx->get("cc_mask", (size_t)np * 4, (void**)&d_good));
+    // {select: 6 (+ 2)} {x, y} {bpmcut, rmscut, stats: 5 (+ 3), negpix}: what comes back is one contiguous run
+    const size_t nback = sizeof(double) * (2 * (size_t)npos + 8) + sizeof(int32_t) * (size_t)npos;
+    ZM_TRY(ctx->get("cc_buf", sizeof(double) * (8 + 2 * (size_t)npos) + nback, (void**)&d_buf));
+    double *d_sel = d_buf, *d_x = d_buf + 8, *d_y = d_x + npos, *d_b = d_y + npos, *d_r = d_b + npos, *d_st = d_r + npos;
+    int32_t* d_n = reinterpret_cast<int32_t*>(d_st + 8);
+    char* h_back = nullptr;
+    ZM_TRY(ctx->get_pinned("cc_back_h", nback, (void**)&h_back));
+    hipStream_t s = ctx->stream;
+    ZM_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * npos, hipMemcpyHostToDevice, s));
+    ZM_HIP(hipMemcpyAsync(d_y, y, sizeof(double) * npos, hipMemcpyHostToDevice, s));
+    const int grid = (int)std::min<int64_t>((np + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_cc_mask, dim3(grid), dim3(256), 0, s, d_mask, bad_bits, np, d_good);
+    ZM_HIP(hipGetLastError());
+    // median of the rms plane over the good pixels and median + MAD of the image, left on the device
+    ZM_TRY(zm_median_mad2_async_dev(ctx, d_rms, d_good, d_img, nullptr, np, d_sel));
+    {
+        zm_scope_timer t(ctx, "candidate_cuts");
+        hipLaunchKernelGGL(k_candidate_cuts, dim3(npos), dim3(64), 0, s, d_img, d_rms, d_mask, bad_bits, nx, ny, npos,
+                           d_x, d_y, d_sel, d_b, d_r, d_n, d_st);
+        ZM_HIP(hipGetLastError());
+    }
+    ZM_HIP(hipMemcpyAsync(h_back, d_b, nback, hipMemcpyDeviceToHost, s));
+    ZM_HIP(hipStreamSynchronize(s));
+    const double* hd = reinterpret_cast<const double*>(h_back);
+    const double* st = hd + 2 * (size_t)npos;
+    ZM_CHECK(st[3] > 0 && st[4] > 0, "zm_candidate_cuts: every pixel is masked");
+    ZM_CHECK(st[2] > 0, "zm_candidate_cuts: sigma must be positive");
+    memcpy(out_bpmcut, hd, sizeof(double) * npos);
+    memcpy(out_rmscut, hd + npos, sizeof(double) * npos);
+    memcpy(out_negpix, st + 8, sizeof(int32_t) * npos);
+    out_stats[0] = st[0]; out_stats[1] = st[1]; out_stats[2] = st[2];
+    return 0;
 }
 
 // ---- host-pointer entry points (small outputs; the image is uploaded once) --------------

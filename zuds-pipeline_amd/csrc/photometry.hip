@@ -5,27 +5,7 @@
 // zuds/constants.py:14).  One wave per position: lanes walk the pixels of the
 // aperture's bounding box, the exact circle / pixel overlap is the closed-form
 // quarter-box area (oracle/photometry.py), sums are wave reductions in fp64.
-#include "zm_internal.h"
-
-__device__ inline double ap_P(double u, double r) {
-    double v = fmax(r * r - u * u, 0.0);
-    double t = fmin(fmax(u / r, -1.0), 1.0);
-    return 0.5 * (u * sqrt(v) + r * r * asin(t));
-}
-
-__device__ inline double ap_quarter(double x, double y, double r) {
-    x = fmin(x, r);
-    y = fmin(y, r);
-    if (x * x + y * y <= r * r) return x * y;
-    double xc = sqrt(fmax(r * r - y * y, 0.0));
-    double xm = fmin(x, xc);
-    return y * xm + ap_P(x, r) - ap_P(xm, r);
-}
-
-__device__ inline double ap_signed(double x, double y, double r) {
-    double s = ((x > 0) - (x < 0)) * ((y > 0) - (y < 0));
-    return s * ap_quarter(fabs(x), fabs(y), r);
-}
+#include "aperture_dev.h"
 
 __global__ __launch_bounds__(64) void k_aperture(const float* __restrict__ img,
                                                  const float* __restrict__ rms,

@@ -255,6 +255,22 @@ class DeviceSubtraction(object):
                                                   wcs=self.wsci if wcs is None else wcs, segm=segm.data_ptr(), **kw)
         return tab, nfound, segm
 
+    def candidates(self, seeing, wcs=None, max_objects=None, **extract_params):
+        """The filtered detection table of the resident difference image: ``extract``, the ``kill_flagged`` rule of
+        ``PipelineFITSCatalog`` (``IMAFLAGS_ISO & BAD_SUM == 0`` and ``FLAGS_WEIGHT == 0``), the pixel cuts on the
+        resident ``diff`` / ``noise`` / ``submask`` (``filterobjects.pixel_cuts_dev``) and ``filter_table`` - what
+        ``PipelineFITSCatalog.from_image`` + ``filter_sexcat`` make of the files, without the planes leaving HBM: the
+        object table, the positions and the per-candidate results are all that crosses PCIe.  ``seeing``: the science
+        FWHM in pixels.  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found)."""
+        from .filterobjects import filter_table, pixel_cuts_dev
+        tab, nfound, _ = self.extract(wcs=wcs, max_objects=max_objects, **extract_params)
+        tab = tab[((tab['IMAFLAGS_ISO'] & self.BAD_SUM) == 0) & (tab['FLAGS_WEIGHT'] == 0)]
+        self.engine.set_stream(self.stream.cuda_stream)
+        with self.torch.cuda.stream(self.stream):
+            pix = pixel_cuts_dev(self.engine, self.diff, self.noise, self.submask, tab['X_IMAGE'], tab['Y_IMAGE'],
+                                 bad_bits=self.BAD_SUM)
+        return filter_table(tab, float(seeing), pix), nfound
+
     def stamps(self, ra, dec, sci, ref, size=63, ref_flxscale=1.0, sci_flxscale=1.0, kernel='LANCZOS3'):
         """The thumbnails of the resident difference image (``Engine.stamps``; scripts/dosub.py:133-150): per position
         the stamps of ``self.diff`` and ``sci`` (science grid, resampled onto the reference grid under the stamps only)

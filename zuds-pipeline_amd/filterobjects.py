@@ -22,7 +22,7 @@ from ._lib import check, ptr
 from .constants import BAD_SUM
 from .engine import get_engine
 
-__all__ = ['pixel_cuts', 'column_cuts', 'filter_sexcat', 'CUTSIZE']
+__all__ = ['pixel_cuts', 'pixel_cuts_dev', 'column_cuts', 'filter_table', 'filter_sexcat', 'CUTSIZE']
 
 CUTSIZE = 11          # pixels, zuds/filterobjects.py:12
 CUT_RADIUS = 6.0      # zuds/filterobjects.py:102-104
@@ -57,6 +57,45 @@ def pixel_cuts(data, rms, bpm, x_image, y_image, engine=None):
     rmscut = rmsbig / area
     good = (bpmbig <= 0) & (rmscut <= medcut) & (neg == 0)
     return dict(BPMCUT=bpmbig, RMSCUT=rmscut, MEDCUT=medcut, NEGPIX=neg, GOODCUT=good.astype(np.uint8))
+
+
+def pixel_cuts_dev(engine, img, rms, mask, x_image, y_image, bad_bits=BAD_SUM):
+    """``pixel_cuts`` on planes that are already in HBM (``zm_candidate_cuts_dev``): ``img`` / ``rms`` float32 and
+    ``mask`` int32 torch tensors on the engine's GPU; a pixel is bad where ``mask & bad_bits``.  The frame statistics
+    are taken on the device and read there by the cuts; only the positions and the per-candidate results cross PCIe.  Enqueued on the stream the engine is bound to and
+    waited for.  Same dict as ``pixel_cuts``; without candidates the kernel is not launched and ``MEDCUT`` comes from the
+    select alone (``zm_median_mad_dev`` on the same planes: the same number)."""
+    import torch
+    for name, t, dt in (('img', img, torch.float32), ('rms', rms, torch.float32), ('mask', mask, torch.int32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != engine.device:
+            raise ValueError(f'{name}: must be a tensor on the engine\'s GPU (cuda:{engine.device})')
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f'{name}: device planes must be contiguous {dt} tensors')
+    if tuple(rms.shape) != tuple(img.shape) or tuple(mask.shape) != tuple(img.shape) or img.dim() != 2:
+        raise ValueError('img, rms and mask must be planes of one shape')
+    ny, nx = (int(v) for v in img.shape)
+    x = np.ascontiguousarray(np.atleast_1d(x_image), dtype=np.float64)
+    y = np.ascontiguousarray(np.atleast_1d(y_image), dtype=np.float64)
+    if x.shape != y.shape:
+        raise ValueError('x_image and y_image must have the same shape')
+    n = x.size
+    bpmcut, rmscut, neg = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+    stats = np.full(3, np.nan)
+    if n == 0:
+        # (zm_candidate_cuts_dev returns at once: the median of the good pixels' rms on its own)
+        good_mask = mask & int(bad_bits)
+        torch.cuda.current_stream(img.device).synchronize()
+        med, mad = C.c_double(), C.c_double()
+        check(engine.L.zm_median_mad_dev(engine.ctx, rms.data_ptr(), good_mask.data_ptr(), nx * ny, C.byref(med),
+                                         C.byref(mad)), 'zm_median_mad_dev')
+        stats[0] = 1.1 * med.value
+    else:
+        check(engine.L.zm_candidate_cuts_dev(engine.ctx, img.data_ptr(), rms.data_ptr(), mask.data_ptr(), int(bad_bits),
+                                             nx, ny, n, ptr(x), ptr(y), ptr(bpmcut), ptr(rmscut), ptr(neg), ptr(stats)),
+              'zm_candidate_cuts_dev')
+    medcut = float(stats[0])
+    good = (bpmcut <= 0) & (rmscut <= medcut) & (neg == 0)
+    return dict(BPMCUT=bpmcut, RMSCUT=rmscut, MEDCUT=medcut, NEGPIX=neg, GOODCUT=good.astype(np.uint8))
 
 
 def column_cuts(table, see, bpmcut, rmscut, medcut):
@@ -104,12 +143,21 @@ def filter_sexcat(cat, engine=None, quiet=False):
         estimate_seeing(image)
     see = image.header['SEEING']
     pix = pixel_cuts(image.data, rms, bpm, table['X_IMAGE'], table['Y_IMAGE'], engine=engine)
+    cat.data = filter_table(table, see, pix, say=say)
+    cat.save()
+    return cat
+
+
+def filter_table(table, see, pix, say=None):
+    """The filter itself, for any route that has the pixel cuts ``pix`` (``pixel_cuts`` / ``pixel_cuts_dev``) of the
+    rows of ``table``: the column cuts in the reference's order, then the negpix cut; returns the table with the
+    ``GOODCUT``, ``BPMCUT``, ``RMSCUT`` and ``rb`` (-99) columns appended.  ``say``: where the reference's count lines
+    go (``filter_sexcat`` prints them)."""
+    say = say or (lambda *a, **k: None)
     good, left = column_cuts(table, see, pix['BPMCUT'], pix['RMSCUT'], pix['MEDCUT'])
     for name, n in left:
         say(f'Number of candidates after {name} cut: ', n)
     good[pix['NEGPIX'] != 0] = 0
     say('Number of candidates after negpix cut: ', int(good.sum()))
-    cat.data = _append_columns(table, GOODCUT=good, BPMCUT=pix['BPMCUT'], RMSCUT=pix['RMSCUT'],
-                               rb=np.full(len(table), -99.0))
-    cat.save()
-    return cat
+    return _append_columns(table, GOODCUT=good, BPMCUT=pix['BPMCUT'], RMSCUT=pix['RMSCUT'],
+                           rb=np.full(len(table), -99.0))

@@ -46,11 +46,21 @@ class SubtractionJob(object):
 
     sci / ref: dicts with ``img``, ``rms``, ``mask`` (int32), ``wcs``; sci also ``wgt`` (for the
     mesh background, may be None) and ``seeing`` (FWHM in pixels); ref optionally ``flxscale``.
-    ``radec``: optional (ra, dec) arrays for forced photometry on the difference image."""
+    ``radec``: optional (ra, dec) arrays for forced photometry on the difference image.
+    ``detect``: the result also carries ``cat``, the filtered detection table of the difference image
+    (``DeviceSubtraction.candidates``: what ``dosub.do_one`` returns for every subtraction of the reference's night,
+    ``scripts/donightly.py:40``).  ``stamps``: and ``stamps``, the thumbnails of its ``GOODCUT == 1`` rows
+    (``DeviceSubtraction.stamps``: dict of blocks [n, 3, S, S], norms, x0, y0, ra, dec); sci optionally ``flxscale``.
+    More than ``max_detections`` such rows: no stamps and ``too_many = True`` (the reference's TooManyDetectionsError,
+    raised after the subtraction's files exist: the products are delivered all the same)."""
 
-    def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None):
+    def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
+                 max_detections=50):
+        if stamps and not detect:
+            raise ValueError('stamps needs detect')
         self.sci, self.ref, self.radec = sci, ref, radec
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag
+        self.detect, self.stamps, self.max_detections = bool(detect), bool(stamps), int(max_detections)
 
 
 class _Worker(object):
@@ -129,10 +139,48 @@ def _collect(w, ch, job, info, diff, noise, mask, keep):
             res_h.copy_(res, non_blocking=True)
             flg_h.copy_(flg, non_blocking=True)
         out['phot'] = dict(x=x, y=y, _pending=(res_h, flg_h, res, flg, pos))
+    if getattr(job, 'detect', False):
+        _detect(ch, job, out)
     if keep:
         with torch.cuda.stream(w.stream):
             out['diff'], out['noise'], out['mask'] = diff.clone(), noise.clone(), mask.clone()
     return out
+
+
+def _detect(ch, job, out):
+    """The detections of a job (``SubtractionJob(detect=True)``), on the chain's stream behind its subtraction.  The
+    object table crosses to the host, so this waits for the chain.  The subtraction's own verdict comes first and is
+    not this function's to judge: a chain whose fit summary is still pending (``run(wait=False)``) is resolved here, and
+    what that raises - a frame without a valid pixel - fails the job as it does without ``detect``.  Only then may the
+    detection step fail on its own (a difference image that is mostly fill value has no spread to cut against): the
+    products of the good subtraction are delivered, with ``cat = None`` and ``detect_error``."""
+    sci, ref = job.sci, job.ref
+    ch.result()
+    try:
+        cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'])
+    except _lib.ZMError as exc:
+        out['cat'], out['detect_error'] = None, str(exc)
+        return
+    out['cat'], out['nfound'] = cat, int(nfound)
+    if not job.stamps:
+        return
+    good = cat[cat['GOODCUT'] == 1]
+    if len(good) > job.max_detections:
+        out['too_many'] = True
+        return
+    ra, dec = np.asarray(good['X_WORLD'], dtype=np.float64), np.asarray(good['Y_WORLD'], dtype=np.float64)
+    if len(good) == 0:
+        S = 63
+        out['stamps'] = dict(blocks=np.zeros((0, 3, S, S), np.float32), norms=np.zeros((0, 3)), ra=ra, dec=dec,
+                             x0=np.zeros(0, np.int32), y0=np.zeros(0, np.int32))
+        return
+    try:
+        blocks, norms, x0, y0 = ch.stamps(ra, dec, sci['img'], ref['img'], ref_flxscale=float(ref.get('flxscale', 1.0)),
+                                          sci_flxscale=float(sci.get('flxscale', 1.0)))
+    except (ValueError, _lib.ZMError) as exc:          # a detection whose stamp misses the reference's grid
+        out['stamps_error'] = str(exc)
+        return
+    out['stamps'] = dict(blocks=blocks, norms=norms, x0=x0, y0=y0, ra=ra, dec=dec)
 
 
 def _settle(out):

@@ -27,6 +27,9 @@ QUANTIF_NMAXLEVELS = 4096
 QUANTIF_AMIN = 4
 BACK_MINGOODFRAC = 0.5
 WEIGHT_THRESH = 1e-30
+# weight planes are float32 and SExtractor holds the threshold in a float: a weight of (float)1e-30, which as a double
+# is 1.0000000032e-30, is AT the threshold, not above it - whatever dtype the caller hands the plane over in
+WEIGHT_THRESH_F32 = float(np.float32(WEIGHT_THRESH))
 EPS = 1e-4
 
 
@@ -90,8 +93,11 @@ def histogram_median_walk(histo, lcut, hcut):
     return hi + 0.5 + frac
 
 
-def backguess(st):
-    """Iterated +-3 sigma clipping on the mesh histogram -> (mode, sigma)."""
+def backguess(st, trace=None):
+    """Iterated +-3 sigma clipping on the mesh histogram -> (mode, sigma).
+
+    ``trace``: a dict that counts, per call, which way the mesh went (see ``mesh_maps``); the result does not
+    depend on it."""
     histo = st['histo']
     nlm1 = st['nlevels'] - 1
     lcut, hcut = 0, nlm1
@@ -121,10 +127,26 @@ def backguess(st):
     if sig > 0:
         if abs((mea - med) / sig) < 0.3:
             mode = qz + (2.5 * med - 1.5 * mea) * qs
+            branch = 'mode'
         else:
             mode = qz + med * qs
+            branch = 'median'
     else:
         mode = qz + mea * qs
+        branch = 'sig0'
+    if trace is not None:
+        trace['meshes'] = trace.get('meshes', 0) + 1
+        trace[branch] = trace.get(branch, 0) + 1
+        # why the loop ended (tested in the order of its condition)
+        if n == 0:
+            trace['it100'] = trace.get('it100', 0) + 1
+        elif sig < 0.1:
+            trace['lowsig'] = trace.get('lowsig', 0) + 1
+        if st['nlevels'] == QUANTIF_NMAXLEVELS:
+            trace['capped'] = trace.get('capped', 0) + 1
+        trace.setdefault('iterations', []).append(100 - n)
+        win = histo[lcut:hcut + 1]
+        trace.setdefault('empty_bin_share', []).append(float((win == 0).mean()) if win.size else 1.0)
     return mode, sig * qs
 
 
@@ -136,8 +158,20 @@ def fqmedian(v):
     return v[n // 2] if n & 1 else 0.5 * (v[n // 2 - 1] + v[n // 2])
 
 
-def mesh_maps(img, wgt=None, mesh=128):
-    """Raw per-mesh (mode, sigma) maps; bad meshes carry -BIG."""
+def _trace_bad(trace):
+    if trace is not None:
+        trace['meshes'] = trace.get('meshes', 0) + 1
+        trace['bad'] = trace.get('bad', 0) + 1
+
+
+def mesh_maps(img, wgt=None, mesh=128, trace=None):
+    """Raw per-mesh (mode, sigma) maps; bad meshes carry -BIG.
+
+    ``trace``: an optional dict, filled with a census of the meshes in row-major order: the counts ``meshes``,
+    ``bad``, ``mode`` / ``median`` / ``sig0`` (the branch of ``backguess`` that gave the value), ``lowsig`` (the clip
+    loop left because sigma fell under 0.1 bins), ``it100`` (100 iterations used up), ``capped`` (4096 levels), and
+    per good mesh the lists ``iterations`` (clip iterations) and ``empty_bin_share`` (share of empty histogram bins
+    inside the final [lcut, hcut]).  The maps do not depend on it."""
     img = np.asarray(img, dtype=np.float64)
     ny, nx = img.shape
     nbx = (nx - 1) // mesh + 1
@@ -151,18 +185,21 @@ def mesh_maps(img, wgt=None, mesh=128):
             p = img[y0:y1, x0:x1].ravel()
             ok = np.abs(p) < BIG            # a sample: not NaN, not +-inf, not <= -BIG (the bad-mesh marker)
             if wgt is not None:
-                ok &= (wgt[y0:y1, x0:x1].ravel() > WEIGHT_THRESH)
+                ok &= (wgt[y0:y1, x0:x1].ravel() > WEIGHT_THRESH_F32)
             p = p[ok]
             area = (y1 - y0) * (x1 - x0)
             if p.size < area * BACK_MINGOODFRAC:
+                _trace_bad(trace)
                 continue
             st = mesh_histogram_stats(p)
             if st is None:
+                _trace_bad(trace)
                 continue
             npix2 = int(st['histo'].sum())
             if npix2 == 0:
+                _trace_bad(trace)
                 continue
-            back[j, i], sigm[j, i] = backguess(st)
+            back[j, i], sigm[j, i] = backguess(st, trace)
     return back, sigm
 
 

@@ -420,7 +420,7 @@ void zo_background(const double* img, const float* wgt, int nx, int ny, int mesh
             for (int y = y0; y < y1; ++y)
                 for (int x = x0; x < x1; ++x) {
                     const double p = img[(size_t)y * nx + x];
-                    if (p > -ZB_BIG && (!wgt || wgt[(size_t)y * nx + x] > (float)WEIGHT_THRESH)) pix[n++] = p;
+                    if (fabs(p) < ZB_BIG && (!wgt || wgt[(size_t)y * nx + x] > (float)WEIGHT_THRESH)) pix[n++] = p;
                 }
             back[m] = sigm[m] = -ZB_BIG;
             if (n < (y1 - y0) * (x1 - x0) * 0.5) continue;

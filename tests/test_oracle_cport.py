@@ -84,6 +84,53 @@ def test_background_matches_numpy(c):
         assert abs(bm - rbm) < 1e-9 * max(1, abs(rbm)) and abs(bs - rbs) < 1e-9 * max(1, abs(rbs))
 
 
+def _same_background(c, img, wgt, mesh):
+    from oracle import background as obk
+    im = img.astype(np.float64)
+    for fsize in (3, 1):
+        b, r, bm, bs, nb, ns = c.background(im, wgt, mesh=mesh, fsize=fsize)
+        rb, rr, rbm, rbs, rnb, rns = obk.background(im, None if wgt is None else wgt.astype(np.float64), mesh=mesh,
+                                                    fsize=fsize)
+        if fsize == 1:
+            # raw mesh maps: without a bad mesh the 1 x 1 filter returns them as they are
+            raw_b, raw_s = obk.mesh_maps(im, None if wgt is None else wgt.astype(np.float64), mesh)
+            good = raw_b > -obk.BIG
+            np.testing.assert_allclose(nb[good], raw_b[good], rtol=1e-9, atol=1e-9)
+            np.testing.assert_allclose(ns[good], raw_s[good], rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(nb, rnb, rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(ns, rns, rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(b, rb, rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(r, rr, rtol=1e-9, atol=1e-9)
+        assert abs(bm - rbm) < 1e-9 * max(1, abs(rbm)) and abs(bs - rbs) < 1e-9 * max(1, abs(rbs))
+
+
+def _regime_scenes():
+    import mesh_scenes as ms
+    return list(ms.SCENES)
+
+
+@pytest.mark.parametrize('name', _regime_scenes())
+def test_background_regimes_match_numpy(c, name):
+    """Every regime of tests/mesh_scenes.py (median branch, sparse histograms, capped levels, sigma under 0.1 bins,
+    constant meshes with NaN / inf pixels, scaled frames) at two mesh sizes, one of them ragged: the two references
+    the GPU tests rest on agree there, on the raw mesh maps and on the final maps."""
+    import mesh_scenes as ms
+    for (nx, ny), mesh in (ms.GEOMETRIES[2], ms.GEOMETRIES[3]):       # 509 x 487 at 64, 512 x 512 at 33
+        img, wgt, census = ms.scene(name, nx, ny, mesh)
+        assert ms.census_ok(name, census, mesh)
+        _same_background(c, img, wgt, mesh)
+
+
+def test_background_good_fraction_and_weight_threshold_match_numpy(c):
+    import mesh_scenes as ms
+    for case in ms.GOOD_FRACTION_CASES:
+        img, wgt, mesh, nbad = ms.good_fraction(*case)
+        assert ms.census(img, wgt, mesh)['bad'] == nbad
+        _same_background(c, img, wgt, mesh)
+        if case[0] == 'full':
+            _same_background(c, img, wgt, 128)
+
+
 # ---- the subtraction leg (oracle/cport/zm_hotpants.c) against oracle/hotpants.py ------------------------------------
 # The C restatement builds the basis vectors with the separable passes the basis allows (as hotpants' xy_conv_stamp and
 # csrc/hp_vectors.hip do) where the numpy oracle correlates 49 two-dimensional kernels: the same definition, sums that

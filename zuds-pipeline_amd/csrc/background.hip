@@ -353,6 +353,9 @@ __device__ __forceinline__ void mesh_general(float (&v)[BKF_PX], const int area,
     double dm = s1 / s0;                                     // mean - K
     double var = s2 / s0 - dm * dm;
     double sig = var > 0 ? sqrt(var) : 0.0;
+    // every sample equals the pivot (the moments about a sample are exact zeros then, and only then: with n <= 16384
+    // samples var >= (K - mean)^2 / n, far above the rounding of s2 / s0 - dm * dm)
+    const bool allsame = sig == 0.0;
     const double lc = K + dm - 2.0 * sig, hc = K + dm + 2.0 * sig;
     // ---- pass 2: 2-sigma clipped
     s0 = s1 = s2 = 0;
@@ -385,10 +388,12 @@ __device__ __forceinline__ void mesh_general(float (&v)[BKF_PX], const int area,
     sig = var > 0 ? sqrt(var) : 0.0;
     const bk_quant q = make_quant(mean, sig, s0);
     if (dbg == 2) { if (sig == 12345.0) D->valid = 7; return; }
-    if (sig == 0.0) {
+    if (allsame) {
         // a constant mesh (flat variance maps, most of the time): qscale = 1 and every pixel
         // falls into bin 0, so backguess returns exactly qzero = (float)mean and sigma 0 -
-        // no histogram, no prefix arrays, no dump
+        // no histogram, no prefix arrays, no dump.  (Not so a mesh that is constant only after the
+        // 2-sigma clip: sigma is 0 and qscale 1 there too, but the histogram takes the clipped pixels
+        // as well, in bins of their own, and backguess returns their mean and spread.)
         if (tid == 0) {
                         D->q = q;
             D->mean0 = (double)(float)mean;

@@ -562,6 +562,63 @@ int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
                int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
                int* out_status);
 
+/* ---- source extraction, second pass: the Kron and windowed columns of sextractor.param ---- */
+/* Opt-in: zm_extract and its table are what they were.  Measures, for rows zm_extract wrote, the columns of
+ * zuds/astromatic/sextractor.param that the isophotal table lacks ("The wide table"; restated in
+ * tests/measure_ref.py).  All sums are float64 over the unfiltered image and the noise plane; bad pixels (the rule of
+ * zm_extract) and pixels outside the frame are skipped; pixels of other objects are not masked (MASK_TYPE NONE).
+ *   Kron      r1 = sum sqrt(r2) v / sum v over the ellipse r2 <= 36 of the isophotal moments; KRON_RADIUS =
+ *             max(kron_fact r1, kron_min_radius); flux sums over r2 <= KRON_RADIUS^2, pixel centres, no sub-pixel weights
+ *   windowed  w = (exact circle overlap, radius 4 sigma_win) x exp(-r^2 / (2 sigma_win^2)); the centre moves by twice
+ *             the weighted first moment until the step is below 1e-4 px, 16 times at the most
+ *   errors    errx2 = sum sigma^2 dx^2 / (sum f)^2 over the member pixels (f: the filtered value), likewise y2, xy */
+typedef struct zm_measure_params {
+    double kron_fact;        /* PHOT_AUTOPARAMS, first value (2.5) */
+    double kron_min_radius;  /* PHOT_AUTOPARAMS, second value (3.5) */
+    int32_t filter;          /* MUST equal zm_extract_params.filter of the run that made the rows: the error sums
+                              * recompute that run's filtered values f from the planes; another value gives
+                              * errx2 / erry2 / errxy (and ERR*_WORLD) of a detection image that was never used */
+    int32_t pad_;
+} zm_measure_params;
+void zm_measure_params_default(zm_measure_params* p);
+
+#define ZM_AUTO_SKIPPED 1        /* flags_auto: more than 10 % of the Kron ellipse's pixels in the frame were skipped */
+#define ZM_AUTO_OFFFRAME 2       /* ... the Kron ellipse leaves the frame */
+#define ZM_AUTO_MINRADIUS 4      /* ... r1 = 0: the minimum radius for lack of positive sums */
+#define ZM_WIN_FALLBACK 1        /* flags_win: the window's weighted sum was not positive: isophotal values */
+#define ZM_WIN_NOTCONVERGED 2    /* ... the step after the 16th iteration was still 1e-4 px or longer */
+
+/* One row of the second pass; row k belongs to rows[k] of the call.  *_image positions are 1-based. */
+typedef struct zm_object_ext {
+    int32_t number;          /* NUMBER of the row this one extends */
+    int32_t npix_auto;       /* pixels summed in FLUX_AUTO */
+    int32_t nskip_auto;      /* bad pixels inside the frame that the Kron ellipse skipped */
+    int32_t flags_auto;      /* FLAGS_AUTO: ZM_AUTO_* */
+    int32_t flags_win;       /* FLAGS_WIN: ZM_WIN_* */
+    int32_t niter_win;       /* centring passes taken */
+    double kron_radius;      /* KRON_RADIUS, in units of the isophotal ellipse */
+    double flux_auto, fluxerr_auto, mag_auto, magerr_auto;
+    double sigma_win;
+    double xwin_image, ywin_image;
+    double x2win, y2win, xywin;              /* window moments (before the 1/12 rule) */
+    double errx2win, erry2win, errxywin;     /* their error moments */
+    double awin_image, bwin_image, thetawin_image;
+    double errawin_image, errbwin_image, errthetawin_image;
+    double errx2, erry2, errxy;              /* isophotal position error moments */
+    double xwin_world, ywin_world;           /* NaN without a WCS, as the three below */
+    double erra_world, errb_world, errtheta_world;   /* degrees; the angle in the local tangent plane */
+} zm_object_ext;
+
+/* img, sigma, bad (uint8, may be NULL), segm_dev (int32: the map zm_extract_dev wrote): device planes of nx x ny
+ * pixels.  rows / out: host arrays of n rows.  n = 0 returns success and writes nothing.  The call waits. */
+int zm_extract_measure_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                           const int32_t* segm_dev, int nx, int ny, const zm_wcs* wcs,
+                           const zm_measure_params* params, int n, const zm_object* rows, zm_object_ext* out);
+/* The same with host planes. */
+int zm_extract_measure(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                       const int32_t* segm, int nx, int ny, const zm_wcs* wcs,
+                       const zm_measure_params* params, int n, const zm_object* rows, zm_object_ext* out);
+
 /* ---- detection thumbnails: stamps of several planes on one grid --------------- */
 /* Replaces the thumbnail step of the subtraction driver (scripts/dosub.py:133-150 -> zuds/thumbnails.py:54-94,133-146):
  * two whole-frame SWarp runs (sub.aligned_to(ref), sci.aligned_to(ref)) and a Cutout2D per detection and image, and the

@@ -2,12 +2,16 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits [--detect [--stamps]]
+usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
 With ``--detect`` every subtraction also gets its detection catalog (``sub.*.cat``, FITS_LDAC) and its filtered
 detections (``PipelineFITSCatalog.from_image`` -> ``Detection.from_catalog``, dosub.py:109-131).
+With ``--param-columns`` (needs ``--detect``) the catalog holds every column of ``sextractor.param`` (``MAG_AUTO``,
+``XWIN_WORLD``, ... : ``extract.PARAM_COLUMNS``) and the ds9 region file ``sub.*.reg`` is written next to it
+once the detections have been filtered (``PipelineRegionFile.from_catalog``: green where ``GOODCUT`` is set, red
+elsewhere).
 With ``--stamps`` (needs ``--detect``) every detection also gets its three thumbnails - difference, new and reference
 image on the reference image's grid (``Thumbnail.from_detections``, dosub.py:133-150) - and ``sub.*.stamps.fits`` is
 written next to the catalog: the zero-filled blocks ``[n, 3, 63, 63]`` (sub, new, ref) and a table with ``ra``, ``dec``,
@@ -65,7 +69,7 @@ def write_stamps(sub, detections, stamps, size=None):
                               [d.dec for d in detections], x0, y0, trimmed)
 
 
-def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False):
+def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -107,11 +111,13 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
     detections = None
     if detect:
         catstart = time.time()
-        cat = zuds.PipelineFITSCatalog.from_image(sub)
+        cat = zuds.PipelineFITSCatalog.from_image(sub, columns='param' if param_columns else 'isophotal')
         catstop = time.time()
         print(f'cat: {catstop - catstart:.2f} sec to make catalog for {sub.basename}', flush=True)
         dstart = time.time()
         detections = zuds.Detection.from_catalog(cat, filter=True)
+        if param_columns:
+            zuds.PipelineRegionFile.from_catalog(cat)     # behind the cuts: green / red by GOODCUT
         if len(detections) > MAX_DETS:
             raise zuds.TooManyDetectionsError(f'Error: {len(detections)} detections (>{MAX_DETS}) '
                                               f'on "{sub.basename}", something wrong with the image probably')
@@ -142,10 +148,14 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
 def main(argv):
     detect = '--detect' in argv
     stamps = '--stamps' in argv
+    param_columns = '--param-columns' in argv
     if stamps and not detect:
         print('--stamps needs --detect', file=sys.stderr)
         return 2
-    args = [a for a in argv if a not in ('--detect', '--stamps')]
+    if param_columns and not detect:
+        print('--param-columns needs --detect', file=sys.stderr)
+        return 2
+    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns')]
     infile = args[0]
     refname = args[1]
     subclass = zuds.SingleEpochSubtraction
@@ -153,7 +163,7 @@ def main(argv):
     imgs = zuds.get_my_share_of_work(infile)
     for fn in imgs:
         try:
-            do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps)
+            do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

@@ -10,6 +10,8 @@ events, per call:
 * ``subtract_ms``  the subtraction leg (``DeviceSubtraction.run``);
 * ``extract_ms``   ``DeviceSubtraction.extract`` on the resident difference, noise and mask planes (object table to the
   host included);
+* ``extract_param_ms``  the same call with ``columns='param'``: the second pass (``k_ex_kron``, ``k_ex_win``) and its
+  table on top; ``param_over_default`` is its ratio to ``extract_ms`` of the same run;
 * ``copy_ms``      a float4 copy (``zm_copy_probe_dev``) that moves the bytes of the planes the extractor has to touch
   at least once: image, noise, flag plane, segmentation map (4 B per pixel each) and the bad-pixel map (1 B).  The copy
   cycles through four source / destination pairs (640 MB in all at the default size), more than the 256 MB last-level
@@ -88,6 +90,10 @@ def main():
         tab, nfound, _ = sub.extract()
         found['n'] = nfound
 
+    def extract_param():
+        tab, nfound, _ = sub.extract(columns='param')
+        found['wide'] = len(tab.dtype.names)
+
     nbytes = (17 * size * size // 2) // 16 * 16
     pairs = [(torch.zeros(nbytes, dtype=torch.uint8, device=device), torch.empty(nbytes, dtype=torch.uint8, device=device))
              for _ in range(4)]
@@ -114,6 +120,7 @@ def main():
 
     s_med, s_min = clock(subtract)
     e_med, e_min = clock(extract)
+    p_med, p_min = clock(extract_param)
     c_med, c_min = clock(copy)
     flat = torch.full((size, size), 100.0, dtype=torch.float32, device=device)
     one = torch.ones((size, size), dtype=torch.float32, device=device)
@@ -128,6 +135,8 @@ def main():
     out = dict(size=size, whole_frame_object_ms=round(w_med, 3), frames=args.frames, steps=args.steps, objects=found.get('n'),
                subtract_ms=round(s_med, 4), subtract_ms_min=round(s_min, 4),
                extract_ms=round(e_med, 4), extract_ms_min=round(e_min, 4),
+               extract_param_ms=round(p_med, 4), extract_param_ms_min=round(p_min, 4), param_columns=found.get('wide'),
+               param_over_default=round(p_med / e_med, 2),
                copy_ms=round(c_med, 4), copy_bytes_per_pixel=17,
                extract_over_subtract=round(e_med / s_med, 3), extract_over_copy=round(e_med / c_med, 2))
     line = json.dumps(out)

@@ -111,6 +111,26 @@ class zm_object(C.Structure):
                 ('fluxerr_aper', C.c_double), ('x_world', C.c_double), ('y_world', C.c_double)]
 
 
+class zm_measure_params(C.Structure):
+    _fields_ = [('kron_fact', C.c_double), ('kron_min_radius', C.c_double), ('filter', C.c_int32), ('pad_', C.c_int32)]
+
+
+class zm_object_ext(C.Structure):
+    """One row of ``zm_extract_measure`` (include/zudsmi.h): the Kron and windowed columns of a ``zm_object``."""
+    _fields_ = [('number', C.c_int32), ('npix_auto', C.c_int32), ('nskip_auto', C.c_int32), ('flags_auto', C.c_int32),
+                ('flags_win', C.c_int32), ('niter_win', C.c_int32),
+                ('kron_radius', C.c_double), ('flux_auto', C.c_double), ('fluxerr_auto', C.c_double),
+                ('mag_auto', C.c_double), ('magerr_auto', C.c_double), ('sigma_win', C.c_double),
+                ('xwin_image', C.c_double), ('ywin_image', C.c_double),
+                ('x2win', C.c_double), ('y2win', C.c_double), ('xywin', C.c_double),
+                ('errx2win', C.c_double), ('erry2win', C.c_double), ('errxywin', C.c_double),
+                ('awin_image', C.c_double), ('bwin_image', C.c_double), ('thetawin_image', C.c_double),
+                ('errawin_image', C.c_double), ('errbwin_image', C.c_double), ('errthetawin_image', C.c_double),
+                ('errx2', C.c_double), ('erry2', C.c_double), ('errxy', C.c_double),
+                ('xwin_world', C.c_double), ('ywin_world', C.c_double),
+                ('erra_world', C.c_double), ('errb_world', C.c_double), ('errtheta_world', C.c_double)]
+
+
 class zm_stamp_plane(C.Structure):
     """One source plane of ``zm_stamps`` / ``zm_stamps_dev`` (include/zudsmi.h)."""
     _fields_ = [('img', C.c_void_p), ('wcs', zm_wcs), ('fscale', C.c_double),
@@ -226,6 +246,11 @@ _SIGS = {
                                  C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'zm_extract': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
                              C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'zm_measure_params_default': (None, [C.POINTER(zm_measure_params)]),
+    'zm_extract_measure_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
+                                         C.POINTER(zm_measure_params), C.c_int, _P, _P]),
+    'zm_extract_measure': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
+                                     C.POINTER(zm_measure_params), C.c_int, _P, _P]),
     'zm_stamp_origin': (C.c_int, [C.POINTER(zm_wcs), C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     'zm_stamps_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_stamp_plane), C.POINTER(zm_wcs), C.c_int, C.c_int, _P, _P,
                                 C.c_int, _P, _P]),

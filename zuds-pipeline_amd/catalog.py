@@ -3,19 +3,55 @@
 ``PipelineFITSCatalog.from_image`` runs the source extractor of libzudsmi (``zm_extract``) where the reference runs
 SExtractor; the table holds the columns that are computed (``extract.CATALOG_COLUMNS``) and no others.  On disk a
 catalog is a FITS_LDAC file, as the reference asks SExtractor for (``catalog_type='FITS_LDAC'``): the object table is
-HDU 2.
+HDU 2.  ``from_image(..., columns='param')`` asks for the wide table (``extract.PARAM_COLUMNS``: every column of
+``sextractor.param``), which ``PipelineRegionFile.from_catalog`` needs.
 """
 from pathlib import Path
+
+import numpy as np
 
 from . import fits as _fits
 from .constants import BAD_SUM, GROUP_PROPERTIES
 from .file import File, UnmappedFileError
 
-__all__ = ['PipelineFITSCatalog']
+__all__ = ['PipelineFITSCatalog', 'PipelineRegionFile']
 
 # what this version of the extractor does not do, stated in every catalog's header
 HEADER_CARDS = [('ZMDEBLND', False, 'multi-threshold deblending (not in this version)'),
                 ('ZMCLEAN', False, 'CLEAN pass (not in this version)')]
+# ... and of a wide table: the Kron and windowed sums do not mask the pixels of other objects
+WIDE_CARDS = [('ZMMASKTY', 'NONE', 'MASK_TYPE of the Kron and windowed sums')]
+
+
+# the two lines every region file starts with (ds9: global properties, then the coordinate system)
+REGION_HEAD = ('global color=green dashlist=8 3 width=1 font="helvetica 10 normal" select=1 highlite=1 dash=0 fixed=0 '
+               'edit=1 move=1 delete=1 include=1 source=1\nicrs\n')
+
+
+class PipelineRegionFile(File):
+    """The ds9 region file of a catalog, ``<catalog>.reg`` next to it (the product of ``zuds/catalog.py:30-65``): one
+    point per row at ``XWIN_WORLD``, ``YWIN_WORLD``; blue for a table that has not been through the cuts, else green
+    where ``GOODCUT`` is set and red where it is not."""
+
+    @classmethod
+    def from_catalog(cls, catalog):
+        tab = catalog.data
+        if not {'XWIN_WORLD', 'YWIN_WORLD'} <= set(tab.dtype.names):
+            raise ValueError("the catalog has no XWIN_WORLD / YWIN_WORLD: make it with columns='param'")
+        reg = cls()
+        reg.basename = catalog.basename.replace('.cat', '.reg')
+        reg.map_to_local_file(str(Path(catalog.local_path).with_name(reg.basename)))
+        for prop in GROUP_PROPERTIES:
+            setattr(reg, prop, getattr(catalog, prop, None))
+        reg.catalog, catalog.regionfile = catalog, reg
+        if 'GOODCUT' in tab.dtype.names:
+            colors = np.where(np.asarray(tab['GOODCUT']) != 0, 'green', 'red')
+        else:
+            colors = np.full(len(tab), 'blue')
+        with open(reg.local_path, 'w') as f:
+            f.write(REGION_HEAD)
+            f.writelines(f'point({ra},{dec}) # color={c}\n' for ra, dec, c in zip(tab['XWIN_WORLD'], tab['YWIN_WORLD'], colors))
+        return reg
 
 
 class PipelineFITSCatalog(File):
@@ -29,11 +65,11 @@ class PipelineFITSCatalog(File):
     image = None
 
     @classmethod
-    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True):
+    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal'):
         from .image import CalibratableImageBase
         if not isinstance(image, CalibratableImageBase):
             raise ValueError('Image is not an instance of CalibratableImage.')
-        image._call_source_extractor(tmpdir=tmpdir, catalog=True)
+        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns)
         cat = image.catalog
         for prop in GROUP_PROPERTIES:
             setattr(cat, prop, getattr(image, prop, None))
@@ -73,7 +109,9 @@ class PipelineFITSCatalog(File):
         except UnmappedFileError:
             f = self.basename
             self.map_to_local_file(f)
-        _fits.write_ldac(f, self.data, self.header or {}, self.header_comments or {}, extra=HEADER_CARDS)
+        wide = 'FLUX_AUTO' in (self.data.dtype.names or ())
+        _fits.write_ldac(f, self.data, self.header or {}, self.header_comments or {},
+                         extra=HEADER_CARDS + (WIDE_CARDS if wide else []))
 
     def kill_flagged(self):
         """Drop the detections with a bad IMAFLAGS_ISO or a bad pixel next to them (``zuds/catalog.py:132-142``); a

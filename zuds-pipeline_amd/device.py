@@ -240,7 +240,8 @@ class DeviceSubtraction(object):
         """Detection catalog of the resident difference image (``Engine.extract_dev``): noise plane as sigma, the
         subtraction mask as flag plane, its ``BAD_SUM`` pixels as bad pixels; nothing but the object table crosses to
         the host.  No background pass: hotpants' difference image carries none.  ``wcs``: the science grid unless
-        given.  Returns (table, number found, segmentation map as an int32 tensor)."""
+        given.  ``columns='param'`` (passed on with ``params``, as kron_fact / kron_min_radius are): the wide table of
+        ``extract.PARAM_COLUMNS``.  Returns (table, number found, segmentation map as an int32 tensor)."""
         torch = self.torch
         self.result()
         ny, nx = self.shape
@@ -261,7 +262,8 @@ class DeviceSubtraction(object):
         resident ``diff`` / ``noise`` / ``submask`` (``filterobjects.pixel_cuts_dev``) and ``filter_table`` - what
         ``PipelineFITSCatalog.from_image`` + ``filter_sexcat`` make of the files, without the planes leaving HBM: the
         object table, the positions and the per-candidate results are all that crosses PCIe.  ``seeing``: the science
-        FWHM in pixels.  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found)."""
+        FWHM in pixels.  ``columns='param'`` among ``extract_params`` keeps the wide table's columns (the cuts read only
+        columns both tables have).  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found)."""
         from .filterobjects import filter_table, pixel_cuts_dev
         tab, nfound, _ = self.extract(wcs=wcs, max_objects=max_objects, **extract_params)
         tab = tab[((tab['IMAFLAGS_ISO'] & self.BAD_SUM) == 0) & (tab['FLAGS_WEIGHT'] == 0)]

@@ -15,7 +15,7 @@ from . import _lib
 from ._lib import as_f32, as_i32, check, ptr, wcs_struct
 from .engine import Engine
 
-__all__ = ['CATALOG_COLUMNS', 'extract_params', 'TooManyDetectionsError']
+__all__ = ['CATALOG_COLUMNS', 'PARAM_COLUMNS', 'extract_params', 'measure_params', 'TooManyDetectionsError']
 
 # column of the catalog <- field of zm_object (include/zudsmi.h); columns that are not computed are absent
 CATALOG_COLUMNS = [('NUMBER', 'number', 'i4'), ('X_IMAGE', 'x_image', 'f8'), ('Y_IMAGE', 'y_image', 'f8'),
@@ -30,6 +30,21 @@ CATALOG_COLUMNS = [('NUMBER', 'number', 'i4'), ('X_IMAGE', 'x_image', 'f8'), ('Y
                    ('IMAFLAGS_ISO', 'imaflags_iso', 'i4')]
 TABLE_DTYPE = np.dtype([(c, t) for c, _, t in CATALOG_COLUMNS])
 MAX_OBJECTS = 1 << 16
+# the wide table (columns='param'): every column of zuds/astromatic/sextractor.param, and the three columns that say how
+# the Kron and windowed values were reached; column <- field of zm_object_ext
+EXT_COLUMNS = [('MAG_AUTO', 'mag_auto', 'f8'), ('MAGERR_AUTO', 'magerr_auto', 'f8'),
+               ('FLUX_AUTO', 'flux_auto', 'f8'), ('FLUXERR_AUTO', 'fluxerr_auto', 'f8'),
+               ('XWIN_IMAGE', 'xwin_image', 'f8'), ('YWIN_IMAGE', 'ywin_image', 'f8'),
+               ('XWIN_WORLD', 'xwin_world', 'f8'), ('YWIN_WORLD', 'ywin_world', 'f8'),
+               ('AWIN_IMAGE', 'awin_image', 'f8'), ('BWIN_IMAGE', 'bwin_image', 'f8'),
+               ('ERRAWIN_IMAGE', 'errawin_image', 'f8'), ('ERRBWIN_IMAGE', 'errbwin_image', 'f8'),
+               ('ERRTHETAWIN_IMAGE', 'errthetawin_image', 'f8'),
+               ('ERRA_WORLD', 'erra_world', 'f8'), ('ERRB_WORLD', 'errb_world', 'f8'),
+               ('ERRTHETA_WORLD', 'errtheta_world', 'f8'),
+               ('KRON_RADIUS', 'kron_radius', 'f8'), ('FLAGS_AUTO', 'flags_auto', 'i4'), ('FLAGS_WIN', 'flags_win', 'i4')]
+PARAM_COLUMNS = CATALOG_COLUMNS + EXT_COLUMNS
+PARAM_DTYPE = np.dtype([(c, t) for c, _, t in PARAM_COLUMNS])
+COLUMN_SETS = ('isophotal', 'param')
 
 
 class TooManyDetectionsError(Exception):
@@ -46,6 +61,49 @@ def extract_params(detect_thresh=1.5, detect_minarea=5, filter=True, satur_level
     p.satur_level = float(satur_level)
     p.aper_radius = float(aper_radius)
     return p
+
+
+def measure_params(kron_fact=2.5, kron_min_radius=3.5, filter=True):
+    """zm_measure_params with the PHOT_AUTOPARAMS of sextractor.conf; ``filter``: as the extraction that made the rows."""
+    p = _lib.zm_measure_params()
+    _lib.lib().zm_measure_params_default(C.byref(p))
+    p.kron_fact = float(kron_fact)
+    p.kron_min_radius = float(kron_min_radius)
+    p.filter = int(bool(filter))
+    return p
+
+
+def _split_params(columns, params):
+    """(extraction keywords, zm_measure_params or None) of a call's ``columns`` and keyword arguments."""
+    if columns not in COLUMN_SETS:
+        raise ValueError(f'columns={columns!r}: one of {COLUMN_SETS}')
+    params = dict(params)
+    if columns != 'param':
+        return params, None
+    mp = measure_params(params.pop('kron_fact', 2.5), params.pop('kron_min_radius', 3.5), params.get('filter', True))
+    return params, mp
+
+
+def ext_to_table(rows, ext, n):
+    """The wide table (``PARAM_COLUMNS``) from the first n rows of a zm_object array and of its zm_object_ext array."""
+    raw = np.frombuffer(rows, dtype=np.dtype(_lib.zm_object), count=n) if n else np.zeros(0, np.dtype(_lib.zm_object))
+    rext = np.frombuffer(ext, dtype=np.dtype(_lib.zm_object_ext), count=n) if n else np.zeros(0, np.dtype(_lib.zm_object_ext))
+    tab = np.zeros(n, dtype=PARAM_DTYPE)
+    for col, field, _ in CATALOG_COLUMNS:
+        tab[col] = raw[field]
+    for col, field, _ in EXT_COLUMNS:
+        tab[col] = rext[field]
+    return tab.view(np.recarray), rext.copy().view(np.recarray)
+
+
+def _measure(self, fn, what, img, sigma, bad, segm, nx, ny, wcs, mp, n):
+    """The second pass on the rows the extraction of this thread has just written: (wide table, zm_object_ext rows)."""
+    rows = self.__dict__['_extract_rows'][threading.get_ident()]
+    ext = (_lib.zm_object_ext * max(n, 1))()
+    w = wcs_struct(wcs) if wcs is not None else None
+    check(fn(self._ctx, img, sigma, bad, segm, nx, ny, C.byref(w) if w is not None else None, C.byref(mp), int(n),
+             C.cast(rows, C.c_void_p), C.cast(ext, C.c_void_p)), what)
+    return ext_to_table(rows, ext, n)
 
 
 def rows_to_table(rows, n):
@@ -72,13 +130,19 @@ def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_object
     return rows_to_table(rows, nw.value), nf.value, st.value
 
 
-def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects=MAX_OBJECTS, full=False, **params):
+def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects=MAX_OBJECTS, full=False,
+                    columns='isophotal', **params):
     """Object table (numpy record array, columns ``CATALOG_COLUMNS``) and segmentation map (int32, 0 = sky) of ``img``
     (background already subtracted) with per-pixel noise ``sigma``, bad-pixel map ``bad`` and flag plane ``flag``.
 
     ``params``: detect_thresh, detect_minarea, filter, satur_level, aper_radius.  More than ``max_objects`` objects:
     the table holds the first ones in NUMBER order, the map all of them.  ``full=True`` returns a dict with the
-    filtered plane, the number found and the status word as well."""
+    filtered plane, the number found and the status word as well.
+
+    ``columns='param'``: the wide table (``PARAM_COLUMNS``: every column of sextractor.param) from a second pass,
+    ``zm_extract_measure``; ``params`` may then carry kron_fact and kron_min_radius (PHOT_AUTOPARAMS), and ``full=True``
+    adds ``ext``, the rows of that pass with every intermediate value."""
+    params, mp = _split_params(columns, params)
     img, sigma, flag = as_f32(img), as_f32(sigma), as_i32(flag)
     ny, nx = img.shape
     if sigma.shape != img.shape:
@@ -93,18 +157,36 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     filt = np.empty((ny, nx), np.float32) if full else None
     tab, nfound, status = _call(self, self.L.zm_extract, 'zm_extract', ptr(img), ptr(sigma), ptr(bad), ptr(flag), nx, ny,
                                 wcs, p, max_objects, ptr(segm), ptr(filt))
+    ext = None
+    if mp is not None:
+        tab, ext = _measure(self, self.L.zm_extract_measure, 'zm_extract_measure', ptr(img), ptr(sigma), ptr(bad),
+                            ptr(segm), nx, ny, wcs, mp, len(tab))
+    if full and ext is not None:
+        return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext)
     if full:
         return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status)
     return tab, segm
 
 
-def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objects=MAX_OBJECTS, segm=None, **params):
+def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objects=MAX_OBJECTS, segm=None,
+                        columns='isophotal', **params):
     """The same on device planes (addresses: float32 img, sigma; uint8 bad or None; int32 flag or None; ``segm``: an
-    int32 device plane that takes the segmentation map, or None).  Returns (table, number found)."""
+    int32 device plane that takes the segmentation map, or None).  Returns (table, number found).
+    ``columns='param'`` needs the segmentation map for its second pass: without ``segm`` a plane is allocated for the
+    call."""
+    params, mp = _split_params(columns, params)
+    own = None
+    if mp is not None and not segm:
+        from . import hipmem
+        own = hipmem.DeviceBuffer(int(nx) * int(ny) * 4)         # (freed when this call returns)
+        segm = own.ptr
     p = extract_params(**params)
     tab, nfound, _ = _call(self, self.L.zm_extract_dev, 'zm_extract_dev', int(img), int(sigma), int(bad) if bad else None,
                            int(flag) if flag else None, int(nx), int(ny), wcs, p, max_objects,
                            int(segm) if segm else None, None)
+    if mp is not None:
+        tab, _ = _measure(self, self.L.zm_extract_measure_dev, 'zm_extract_measure_dev', int(img), int(sigma),
+                          int(bad) if bad else None, int(segm), int(nx), int(ny), wcs, mp, len(tab))
     return tab, nfound
 
 

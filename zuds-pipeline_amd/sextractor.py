@@ -11,6 +11,8 @@ filter ``default.conv``, ``DETECT_THRESH`` 1.5, ``DETECT_MINAREA`` 5, no deblend
 ``SATUR_LEVEL``, ``BACK_SIZE``, ``BACK_FILTERSIZE`` are honoured; keys that would change something this version does
 not do (``DEBLEND_*``, ``CLEAN*``, ``MASK_TYPE``, ``FILTER_NAME``, a ``WEIGHT_TYPE`` other than ``MAP_WEIGHT``, an
 ``ANALYSIS_THRESH`` different from ``DETECT_THRESH``) raise ``ValueError``; bookkeeping keys are ignored.
+``columns='param'`` asks for the wide table (``extract.PARAM_COLUMNS``: every column of ``sextractor.param``); only then
+may ``sextractor_kws`` carry ``PHOT_AUTOPARAMS`` (two values).
 """
 import os
 
@@ -96,14 +98,40 @@ def prepare_sextractor(image, directory=None, checkimage_type=None,
                 outnames=outnames, types=checkimage_types)
 
 
-def _extract(image, call, sub, sextractor_kws):
+def measurement_settings(sextractor_kws=None):
+    """(``sextractor_kws`` without the keys of the second pass, keyword arguments of that pass) for ``columns='param'``."""
+    rest, auto = {}, None
+    for k, v in (sextractor_kws or {}).items():
+        if str(k).upper() == 'PHOT_AUTOPARAMS':
+            auto = v
+        else:
+            rest[k] = v
+    if auto is None:
+        return rest, {}
+    if isinstance(auto, str):
+        auto = auto.split(',')
+    auto = np.atleast_1d(auto).astype(float)
+    if auto.size != 2 or not (auto > 0).all():
+        raise ValueError('sextractor_kws: PHOT_AUTOPARAMS takes two positive values (Kron factor, minimum radius)')
+    return rest, dict(kron_fact=float(auto[0]), kron_min_radius=float(auto[1]))
+
+
+def _extract(image, call, sub, sextractor_kws, columns='isophotal'):
     """(PipelineFITSCatalog, segmentation map) of the background-subtracted plane ``sub``: noise = the image's
     rms_image, bad = weight 0, flags = the mask."""
     from .catalog import PipelineFITSCatalog
     from .engine import get_engine
     if call['catalog_type'] != 'FITS_LDAC':
         raise ValueError(f'catalog_type "{call["catalog_type"]}": only FITS_LDAC catalogs are written')
+    if columns == 'param':
+        sextractor_kws, second = measurement_settings(sextractor_kws)
+        second['columns'] = 'param'
+    elif columns == 'isophotal':
+        second = {}
+    else:
+        raise ValueError(f"columns={columns!r}: 'isophotal' or 'param'")
     settings = extraction_settings(sextractor_kws, image.header)
+    settings.update(second)
     mask = getattr(image, 'mask_image', None)
     try:
         wcs = image.wcs
@@ -124,11 +152,11 @@ def _extract(image, call, sub, sextractor_kws):
 
 
 def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir='/tmp',
-                   use_weightmap=True, sextractor_kws=None, catalog=False):
+                   use_weightmap=True, sextractor_kws=None, catalog=False, columns='isophotal'):
     """Produce the requested check-images as FITSImage objects, written next to
     the image when it is mapped (``zuds/sextractor.py:110-150``).  The returned
     list starts with the catalog slot: ``None``, or with ``catalog=True`` (or when ``segm`` is among the
-    check-images) the ``PipelineFITSCatalog`` of the image."""
+    check-images) the ``PipelineFITSCatalog`` of the image; ``columns='param'``: with the wide table."""
     from .engine import get_engine
     from .image import FITSImage
     call = prepare_sextractor(image, None, checkimage_type=checkimage_type,
@@ -146,7 +174,7 @@ def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir
     planes = {'bkg': bkg, 'rms': rms, 'bkgsub': sub}
     result = [None]
     if extracting:
-        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws)
+        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws, columns)
     for t, name in zip(call['types'], call['outnames']):
         product = FITSImage()
         product.basename = os.path.basename(name)

@@ -95,12 +95,15 @@ def convolve_true(img, k):
     return correlate2d(img, k[::-1, ::-1], mode='valid')
 
 
-def clipped_moments(v, nsig=3.0, passes=3):
+def clipped_moments(v, nsig=3.0, passes=3, log=None):
+    """``log``: a list that receives the (m, s) each pass clips with (the trace of fit_region)."""
     v = np.asarray(v, dtype=np.float64)
     if v.size == 0:
         return 0.0, 0.0
     m, s = v.mean(), v.std()
     for _ in range(passes):
+        if log is not None:
+            log.append((float(m), float(s)))
         sel = v[np.abs(v - m) <= nsig * s]
         if sel.size == 0:
             break
@@ -245,14 +248,20 @@ def stamp_merit(st, x, nc, nbg, kterms):
     return ss / (st['npix'] * st['vbar'])
 
 
-def fit_region(sci, ref, svar, tvar, ok, reg, basis, p):
-    """Kernel solution of one region: (x, kterms, info) or None if unsolvable."""
+def fit_region(sci, ref, svar, tvar, ok, reg, basis, p, trace=None):
+    """Kernel solution of one region: (x, kterms, info) or None if unsolvable.
+
+    ``trace``: a list that receives one record per round - the live stamps, each one's ``active`` substamp index,
+    substamp centre, merit and ``vbar``, the (m, s) of every clipping pass, the limit ``m + ks s`` and the rejected
+    stamps - and, as its first entry, the candidate centres of every stamp cell.  It changes no result."""
     nc = basis.shape[0]
     nbg = len(poly_terms(p['bgo']))
     cands = find_substamps(ref, ok, reg, p)
     ntotal = sum(1 for c in cands if c)
     active = [0 if c else -1 for c in cands]
     cache = {}
+    if trace is not None:
+        trace.append(dict(cands=[list(c) for c in cands]))
 
     def system(si):
         key = (si, active[si])
@@ -275,8 +284,14 @@ def fit_region(sci, ref, svar, tvar, ok, reg, basis, p):
         fitted = list(live)
         x, kterms = solve_region(systems, nc, nbg, p['ko'])
         merits = np.array([stamp_merit(st, x, nc, nbg, kterms) for st in systems])
-        m, s = clipped_moments(merits)
+        clips = [] if trace is not None else None
+        m, s = clipped_moments(merits, log=clips)
         rej = [si for si, mm in zip(live, merits) if mm > m + p['ks'] * s]
+        if trace is not None:
+            trace.append(dict(round=rounds, live=list(live), active=[active[si] for si in live],
+                              centres=[(st['cx'], st['cy']) for st in systems], merits=merits.copy(),
+                              vbar=[st['vbar'] for st in systems], clips=clips, limit=float(m + p['ks'] * s),
+                              rejected=list(rej)))
         if not rej:
             break
         for si in rej:
@@ -301,8 +316,9 @@ def kernel_at(x, kterms, basis, fx, fy):
     return np.tensordot(c, basis, axes=1)
 
 
-def subtract(sci, ref, sci_rms, ref_rms, bpm, **kw):
-    """Full difference image.  Returns (diff, noise, info)."""
+def subtract(sci, ref, sci_rms, ref_rms, bpm, trace=False, **kw):
+    """Full difference image.  Returns (diff, noise, info).  ``trace=True``: info['traces'] holds the per-round
+    record of every region's fit (see fit_region), also of a region that came out unsolved."""
     p = params(**kw)
     sci = np.asarray(sci, dtype=np.float64)
     ref = np.asarray(ref, dtype=np.float64)
@@ -323,11 +339,13 @@ def subtract(sci, ref, sci_rms, ref_rms, bpm, **kw):
     outbad[:, :hwk] = True
     outbad[:, nx - hwk:] = True
     infos = []
+    traces = []
     step = 2 * hwk + 1
     refz = np.where(np.isfinite(ref), ref, 0.0)
     tvz = np.where(np.isfinite(tvar), tvar, 0.0)
     for reg in regions(nx, ny, p['nrx'], p['nry']):
-        fit = fit_region(sci, ref, svar, tvar, ok, reg, basis, p)
+        traces.append([] if trace else None)
+        fit = fit_region(sci, ref, svar, tvar, ok, reg, basis, p, trace=traces[-1])
         if fit is None:
             infos.append(None)
             continue
@@ -360,4 +378,7 @@ def subtract(sci, ref, sci_rms, ref_rms, bpm, **kw):
                 good = ~outbad[by:ey, bx:ex]
                 diff[by:ey, bx:ex] = np.where(good, d, p['fi'])
                 noise[by:ey, bx:ex] = np.where(good, nz, p['fin'])
-    return diff, noise, dict(regions=infos, nmasked=int((diff == p['fi']).sum()))
+    out = dict(regions=infos, nmasked=int((diff == p['fi']).sum()))
+    if trace:
+        out['traces'] = traces
+    return diff, noise, out

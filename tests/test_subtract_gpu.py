@@ -41,7 +41,8 @@ def scene(nx=384, ny=352, seed=1, nstars=120, ksig=0.9, scale=1.3, bg=20.0,
             ref.astype(np.float32), np.full((ny, nx), 0.5, np.float32), bpm)
 
 
-def compare(engine, data, tol=1e-5, got=None, **kw):
+def compare(engine, data, tol=1e-5, got=None, chi2_tol=None, **kw):
+    """``chi2_tol`` (opt-in): ``info['chi2']`` against the mean of the oracle's regions, relative."""
     sci, srms, ref, rrms, bpm = data
     d, n, info = got if got is not None else engine.subtract(sci, srms, ref, rrms, bpm, **kw)
     rd, rn, rinfo = ohp.subtract(sci, ref, srms, rrms, bpm, **kw)
@@ -55,6 +56,9 @@ def compare(engine, data, tol=1e-5, got=None, **kw):
     assert info['nmasked'] == rinfo['nmasked']
     ks = np.mean([r['kernel_sum'] for r in regs])
     assert abs(info['kernel_sum'] - ks) < 1e-6 * abs(ks)
+    if chi2_tol is not None:
+        chi2 = np.mean([r['chi2'] for r in regs])
+        assert abs(info['chi2'] - chi2) <= chi2_tol * abs(chi2), f"chi2 {info['chi2']!r} against {chi2!r}"
     good = ~gm
     scale = np.abs(sci.astype(np.float64)) + np.abs(sci.astype(np.float64) - rd)
     err = np.abs(d.astype(np.float64) - rd)[good]

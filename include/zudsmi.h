@@ -656,6 +656,53 @@ int zm_stamps(zm_ctx* ctx, int nplanes, const zm_stamp_plane* planes, const zm_w
               int kernel, int n, const int32_t* x0, const int32_t* y0, int size,
               float* out, double* out_norm);
 
+/* ---- real / bogus score: the braai network behind the candidate cuts ----------- */
+/* Replaces ml_model.predict(make_triplet_for_braai(...)) of the candidate filter (zuds/filterobjects.py:196-240):
+ * forward inference, exact fp32 with fp32 accumulation in a fixed order, of a sequential model made of
+ *   Conv2D        3 x 3, 'valid', stride 1, bias, relu or linear;
+ *   MaxPooling2D  square, stride = size, 'valid' (an odd remainder is dropped, as Keras does);
+ *   Flatten       channels-last order (h, w, c);
+ *   Dense         relu, sigmoid or linear;
+ * at most 64 channels per convolution, 4096 units per Dense layer; the first layer is a Conv2D, the last a Dense of
+ * one unit.  Anything else is refused by zm_rb_model_create with a message (zm_last_error).  Dropout is identity at
+ * inference: leave it out of the list.
+ * Input: the stamp blocks as zm_stamps_dev writes them, [n][nplanes][S][S] float32 and [n][nplanes] float64 norms;
+ * channel c of the network is plane plane_of_channel[c] divided by (float)norm, as the first convolution reads it.
+ * A triplet of which a used norm is zero or not finite scores NaN, by an explicit test (NaN < cut is false: such a
+ * row keeps its GOODCUT, as in the reference, whose cutout / norm is a plane of NaN).
+ * The score of a triplet has the same bits alone, first, last or anywhere in a batch; two runs give the same bytes.
+ * Batches are worked through in chunks of at most ZM_RB_CHUNK triplets; the activations between launches live in two
+ * scratch slots of the context that never grow beyond ZM_RB_CHUNK x (largest activation of the even launches +
+ * largest of the odd ones) floats: 128 x (61 x 61 x 16 + 29 x 29 x 16) x 4 bytes = 37 MB for braai's VGG6. */
+#define ZM_RB_CHUNK 128
+enum { ZM_RB_CONV2D = 1, ZM_RB_MAXPOOL = 2, ZM_RB_FLATTEN = 3, ZM_RB_DENSE = 4 };
+enum { ZM_RB_LINEAR = 0, ZM_RB_RELU = 1, ZM_RB_SIGMOID = 2 };
+enum { ZM_RB_VALID = 0, ZM_RB_SAME = 1 };
+typedef struct zm_rb_layer {
+    int32_t type;          /* ZM_RB_CONV2D ... */
+    int32_t activation;    /* ZM_RB_LINEAR ... (Conv2D, Dense) */
+    int32_t cin, cout;     /* Conv2D: channels in / out; Dense: inputs / units; else 0 */
+    int32_t pool;          /* MaxPooling2D: window size; else 0 */
+    int32_t ksize;         /* Conv2D: kernel size (3) */
+    int32_t stride;        /* Conv2D: 1; MaxPooling2D: = pool */
+    int32_t padding;       /* ZM_RB_VALID */
+    int64_t w_off, b_off;  /* first float of the kernel / of the bias in the blob; Keras layouts: Conv2D kernels
+                              [kh][kw][cin][cout], Dense kernels [in][out] */
+} zm_rb_layer;
+typedef struct zm_rb_model zm_rb_model;
+/* validates the shape chain and every limit, re-lays the weights for the kernels and uploads them once (the call waits) */
+int zm_rb_model_create(zm_ctx* ctx, int in_size, int in_channels, int nlayers, const zm_rb_layer* layers,
+                       const float* weights, int64_t nweights, zm_rb_model** out);
+int zm_rb_model_destroy(zm_rb_model* model);
+/* blocks_dev, norms_dev, rb_dev [n] float32: device memory; plane_of_channel: host array of in_channels entries (3 for
+ * braai: the planes that hold new, ref, sub).  Enqueued on the context's stream, nothing waited for.  n = 0: nothing
+ * happens. */
+int zm_rb_score_dev(zm_ctx* ctx, const zm_rb_model* model, int n, const float* blocks_dev, const double* norms_dev,
+                    int nplanes, const int32_t* plane_of_channel, float* rb_dev);
+/* the same on host arrays: copied in, the call waits */
+int zm_rb_score(zm_ctx* ctx, const zm_rb_model* model, int n, const float* blocks, const double* norms,
+                int nplanes, const int32_t* plane_of_channel, float* rb);
+
 /* ---- FITS data blocks on the device ------------------------------------------ */
 /* Replaces the host-side decode / encode astropy does inside FITSFile.load_data / save
  * (zuds/fitsfile.py:69-94,146-206): raw_dev holds the big-endian data block of a primary

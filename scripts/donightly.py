@@ -6,7 +6,7 @@ subtractions as one batch of launches on each of J lanes (``nightly.SubtractionP
 ``--fit-batch 0``: J separate subtractions in flight).
 
 usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch B] [--batch FRAMES] [--nreg-side N]
-                    [--detect [--stamps]]
+                    [--detect [--stamps] [--rb-model BASE [--rb-cut X]]]
 
 * ``images.txt``: science image paths (``*sciimg.fits``; the mask is ``*mskimg.fits``; a
   ``.weight.fits`` sibling is required: 1 / rms^2, 0 on bad pixels).  The list is sharded over
@@ -182,9 +182,19 @@ def main(argv=None):
                          'groups, two lanes of 16 1.95 / 2.8, 8 - 16 separate chains 3.0); 0: one chain per job')
     ap.add_argument('--detect', action='store_true', help='write the filtered detection catalog sub.*.cat of every subtraction')
     ap.add_argument('--stamps', action='store_true', help='with --detect: write sub.*.stamps.fits, the thumbnails of the detections')
+    ap.add_argument('--rb-model', help='with --detect: BASE of BASE.architecture.json + BASE.weights.npz, the real / bogus '
+                                       'network the candidate filter ends with (realbogus.load_model)')
+    ap.add_argument('--rb-cut', type=float, help='with --rb-model: the score below which a candidate is cut; default '
+                                                 'RB_CUT of the frame\'s FID / FILTERID card (a frame without one is an error)')
     args = ap.parse_args(argv)
     if args.stamps and not args.detect:
         print('--stamps needs --detect', file=sys.stderr)
+        return 2
+    if (args.rb_model or args.rb_cut is not None) and not args.detect:
+        print('--rb-model needs --detect', file=sys.stderr)
+        return 2
+    if args.rb_cut is not None and not args.rb_model:
+        print('--rb-cut needs --rb-model', file=sys.stderr)
         return 2
 
     nightly = importlib.import_module('zuds-pipeline_amd.nightly')
@@ -203,15 +213,17 @@ def main(argv=None):
     ref = load_reference(io, args.refname)
     pool = nightly.SubtractionPool(args.jobs, device=local, batch=args.fit_batch)
     ring = importlib.import_module('zuds-pipeline_amd.fitsring').FITSRing(local)
+    rb_model = zuds.load_model(args.rb_model) if args.rb_model else None
     try:
         return run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side,
-                         detect=args.detect, stamps=args.stamps)
+                         detect=args.detect, stamps=args.stamps, rb_model=rb_model, rb_cut=args.rb_cut)
     finally:
         pool.close()
         ring.close()
 
 
-def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False):
+def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False, rb_model=None,
+              rb_cut=None):
     """The images of this rank against one reference.  The files of batch b + 1 are read, sent and decoded by the
     ring (fitsring.FITSRing: reader threads, copy stream) while the pool subtracts batch b; the products of batch b
     are encoded on the device, copied back on a third stream and written by the ring's writer threads while
@@ -264,14 +276,19 @@ def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, dete
                         raise item
                 (img, hdr), (mask, _), (wgt, _) = trio
                 sci = finish_science(io, fn, img, hdr, mask, wgt)
+                rbkw = {}
+                if rb_model is not None:
+                    # the filter id as image.py reads it; a frame without the card and no --rb-cut fails here (ValueError)
+                    rbkw = dict(rb_model=rb_model, rb_cut=rb_cut, fid=hdr.get('FID', hdr.get('FILTERID')))
+                job = nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
+                                             stamps=stamps, max_detections=MAX_DETS, **rbkw)
             except Exception:
                 # (the reference's drivers: try / except per image, scripts/dosub.py:205-213)
                 traceback.print_exception(*sys.exc_info())
                 continue
             sci['radec'] = radec
             scis.append(sci)
-            jobs.append(nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
-                                               stamps=stamps, max_detections=MAX_DETS))
+            jobs.append(job)
         io.stream.synchronize()                  # (the rms maps; the pool's lanes read them on their own streams)
         return scis, jobs, (1e3 * (t1 - t0), 1e3 * (time.time() - t1))
     finisher = ThreadPoolExecutor(1, thread_name_prefix='zmnight-fin')

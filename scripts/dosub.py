@@ -2,7 +2,7 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns]]
+usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns] [--rb-model BASE [--rb-cut X]]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
@@ -16,6 +16,10 @@ With ``--stamps`` (needs ``--detect``) every detection also gets its three thumb
 image on the reference image's grid (``Thumbnail.from_detections``, dosub.py:133-150) - and ``sub.*.stamps.fits`` is
 written next to the catalog: the zero-filled blocks ``[n, 3, 63, 63]`` (sub, new, ref) and a table with ``ra``, ``dec``,
 ``x0``, ``y0`` and the shape of the stamp trimmed to the grid.
+With ``--rb-model BASE`` (needs ``--detect``) the filter ends with the real / bogus network stored as
+``BASE.architecture.json`` + ``BASE.weights.npz`` (``realbogus.load_model``): ``rb`` is the score, and rows below
+``--rb-cut X`` - or ``RB_CUT`` of the frame's ``FID`` / ``FILTERID`` card - are cut (``filterobjects.py:196-240``).  A frame
+without that card and no ``--rb-cut`` is an error.
 """
 import os
 import sys
@@ -69,7 +73,8 @@ def write_stamps(sub, detections, stamps, size=None):
                               [d.dec for d in detections], x0, y0, trimmed)
 
 
-def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False):
+def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
+           rb_cut=None):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -115,7 +120,9 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
         catstop = time.time()
         print(f'cat: {catstop - catstart:.2f} sec to make catalog for {sub.basename}', flush=True)
         dstart = time.time()
-        detections = zuds.Detection.from_catalog(cat, filter=True)
+        if rb_model is not None:
+            zuds.rb_cut_for(getattr(sub, 'fid', None), rb_cut)      # a missing FID card and no --rb-cut: an error, here
+        detections = zuds.Detection.from_catalog(cat, filter=True, rb_model=rb_model, rb_cut=rb_cut)
         if param_columns:
             zuds.PipelineRegionFile.from_catalog(cat)     # behind the cuts: green / red by GOODCUT
         if len(detections) > MAX_DETS:
@@ -155,6 +162,28 @@ def main(argv):
     if param_columns and not detect:
         print('--param-columns needs --detect', file=sys.stderr)
         return 2
+    argv = list(argv)
+    rb_model = rb_cut = None
+    for flag in ('--rb-model', '--rb-cut'):
+        if flag in argv:
+            k = argv.index(flag)
+            if k + 1 >= len(argv):
+                print(f'{flag} needs a value', file=sys.stderr)
+                return 2
+            value = argv[k + 1]
+            del argv[k:k + 2]
+            if flag == '--rb-model':
+                rb_model = value
+            else:
+                rb_cut = float(value)
+    if (rb_model or rb_cut is not None) and not detect:
+        print('--rb-model needs --detect', file=sys.stderr)
+        return 2
+    if rb_cut is not None and not rb_model:
+        print('--rb-cut needs --rb-model', file=sys.stderr)
+        return 2
+    if rb_model:
+        rb_model = zuds.load_model(rb_model)
     args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns')]
     infile = args[0]
     refname = args[1]
@@ -163,7 +192,8 @@ def main(argv):
     imgs = zuds.get_my_share_of_work(infile)
     for fn in imgs:
         try:
-            do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns)
+            do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
+                   rb_model=rb_model, rb_cut=rb_cut)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

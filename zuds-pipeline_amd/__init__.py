@@ -28,6 +28,7 @@ from .filterobjects import *
 from .catalog import *
 from .detections import *
 from .thumbnails import *
+from .realbogus import *
 from . import synth, fits
 
 # same DB-free entry points as the reference

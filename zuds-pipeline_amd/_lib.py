@@ -137,6 +137,17 @@ class zm_stamp_plane(C.Structure):
                 ('on_grid', C.c_int32), ('pad_', C.c_int32)]
 
 
+class zm_rb_layer(C.Structure):
+    """One layer of ``zm_rb_model_create`` (include/zudsmi.h)."""
+    _fields_ = [('type', C.c_int32), ('activation', C.c_int32), ('cin', C.c_int32), ('cout', C.c_int32),
+                ('pool', C.c_int32), ('ksize', C.c_int32), ('stride', C.c_int32), ('padding', C.c_int32),
+                ('w_off', C.c_int64), ('b_off', C.c_int64)]
+
+
+RB_CHUNK = 128                                         # ZM_RB_CHUNK
+RB_CONV2D, RB_MAXPOOL, RB_FLATTEN, RB_DENSE = 1, 2, 3, 4
+RB_ACTIVATION = {'linear': 0, 'relu': 1, 'sigmoid': 2}
+RB_VALID, RB_SAME = 0, 1
 STAMP_MAX, STAMP_PLANES_MAX = 256, 8                   # ZM_STAMP_MAX, ZM_STAMP_PLANES_MAX
 STAMP_NOT_FINITE, STAMP_NO_OVERLAP = 1, 2              # zm_stamp_origin status words
 EXTRACT_CHAIN = 1                                      # zm_extract status bit (ZM_EXTRACT_CHAIN)
@@ -256,6 +267,10 @@ _SIGS = {
                                 C.c_int, _P, _P]),
     'zm_stamps': (C.c_int, [_P, C.c_int, C.POINTER(zm_stamp_plane), C.POINTER(zm_wcs), C.c_int, C.c_int, _P, _P,
                             C.c_int, _P, _P]),
+    'zm_rb_model_create': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(zm_rb_layer), _P, C.c_int64, C.POINTER(C.c_void_p)]),
+    'zm_rb_model_destroy': (C.c_int, [_P]),
+    'zm_rb_score_dev': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    'zm_rb_score': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
     'zm_timing_enable': (C.c_int, [_P, C.c_int]),
     'zm_timing_filter': (C.c_int, [_P, C.c_char_p]),
     'zm_timing_reset': (C.c_int, [_P]),

@@ -39,3 +39,7 @@ MASK_COMMENTS = {
 }
 
 REFERENCE_VERSION = 'zuds5'
+
+# the real / bogus cut of the candidate filter (zuds/constants.py:18-21): per filter id, and the model it was set for
+RB_CUT = {1: 0.3, 2: 0.3, 3: 0.6}
+BRAAI_MODEL = 'braai_d6_m9'

@@ -16,6 +16,7 @@ class Detection(object):
         self.x_image, self.y_image = x_image, y_image
         self.goodcut = None
         self.rb = None
+        self.rb_version = None
 
     @property
     def snr(self):
@@ -25,11 +26,13 @@ class Detection(object):
         return f'<Detection x={self.x_image:.2f} y={self.y_image:.2f} snr={self.snr:.1f}>'
 
     @classmethod
-    def from_catalog(cls, cat, filter=True):
+    def from_catalog(cls, cat, filter=True, rb_model=None, rb_cut=None):
         """The detections of ``cat``; with ``filter`` the catalog goes through ``filter_sexcat`` first and only rows
-        with ``GOODCUT == 1`` are returned."""
+        with ``GOODCUT == 1`` are returned.  ``rb_model``: the real / bogus model the filter scores with; its base name
+        is kept as ``rb_version`` beside ``rb`` (``zuds/detections.py:99``)."""
         if filter:
-            filter_sexcat(cat)
+            filter_sexcat(cat, rb_model=rb_model, rb_cut=rb_cut)
+        version = rb_model.name if rb_model is not None else getattr(cat, 'rb_version', None)
         names = cat.data.dtype.names
         result = []
         for row in cat.data:
@@ -42,6 +45,7 @@ class Detection(object):
                     b_image=float(row['B_IMAGE']), fwhm_image=float(row['FWHM_IMAGE']),
                     x_image=float(row['X_IMAGE']), y_image=float(row['Y_IMAGE']))
             d.rb = float(row['rb']) if 'rb' in names else None
+            d.rb_version = version if d.rb is not None and d.rb != -99.0 else None
             if filter:
                 d.goodcut = True
             result.append(d)

@@ -256,38 +256,61 @@ class DeviceSubtraction(object):
                                                   wcs=self.wsci if wcs is None else wcs, segm=segm.data_ptr(), **kw)
         return tab, nfound, segm
 
-    def candidates(self, seeing, wcs=None, max_objects=None, **extract_params):
+    def candidates(self, seeing, wcs=None, max_objects=None, rb_model=None, sci=None, ref=None, fid=None, rb_cut=None,
+                   sci_flxscale=1.0, **extract_params):
         """The filtered detection table of the resident difference image: ``extract``, the ``kill_flagged`` rule of
         ``PipelineFITSCatalog`` (``IMAFLAGS_ISO & BAD_SUM == 0`` and ``FLAGS_WEIGHT == 0``), the pixel cuts on the
         resident ``diff`` / ``noise`` / ``submask`` (``filterobjects.pixel_cuts_dev``) and ``filter_table`` - what
         ``PipelineFITSCatalog.from_image`` + ``filter_sexcat`` make of the files, without the planes leaving HBM: the
         object table, the positions and the per-candidate results are all that crosses PCIe.  ``seeing``: the science
         FWHM in pixels.  ``columns='param'`` among ``extract_params`` keeps the wide table's columns (the cuts read only
-        columns both tables have).  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found)."""
-        from .filterobjects import filter_table, pixel_cuts_dev
+        columns both tables have).  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found).
+        ``rb_model`` (``realbogus.RBModel``; needs ``sci`` and ``ref``, the tensors handed to ``run``): behind the pixel
+        cuts the surviving rows are stamped on this chain's stream (``zm_stamps_dev``), scored where the blocks lie
+        (``zm_rb_score_dev``) and cut at ``rb_cut`` or ``RB_CUT[fid]`` (``zuds/filterobjects.py:196-240``); ``rb[n]`` is
+        all that is read back.  A surviving row whose stamp misses the reference's grid raises ``ValueError``."""
+        from .filterobjects import filter_table, good_before_ml, pixel_cuts_dev, rb_cut_for
+        if rb_model is not None:
+            if sci is None or ref is None:
+                raise ValueError('candidates(rb_model=...) needs the sci and ref tensors for the stamps')
+            cut = rb_cut_for(fid, rb_cut)
         tab, nfound, _ = self.extract(wcs=wcs, max_objects=max_objects, **extract_params)
         tab = tab[((tab['IMAFLAGS_ISO'] & self.BAD_SUM) == 0) & (tab['FLAGS_WEIGHT'] == 0)]
         self.engine.set_stream(self.stream.cuda_stream)
         with self.torch.cuda.stream(self.stream):
             pix = pixel_cuts_dev(self.engine, self.diff, self.noise, self.submask, tab['X_IMAGE'], tab['Y_IMAGE'],
                                  bad_bits=self.BAD_SUM)
-        return filter_table(tab, float(seeing), pix), nfound
+        if rb_model is None:
+            return filter_table(tab, float(seeing), pix), nfound
+        rows = tab[good_before_ml(tab, float(seeing), pix) > 0]
+        rb = np.zeros(0)
+        if len(rows):
+            blocks, norms, _, _ = self.stamps(np.asarray(rows['X_WORLD'], np.float64), np.asarray(rows['Y_WORLD'], np.float64),
+                                              sci, ref, size=rb_model.in_size, sci_flxscale=sci_flxscale, device_out=True)
+            with self.torch.cuda.stream(self.stream):
+                rb_dev = rb_model.score_dev(blocks, norms, order=('sub', 'new', 'ref'), engine=self.engine, stream=self.stream)
+                rb_host = rb_dev.cpu()
+            self.stream.synchronize()
+            rb = rb_host.numpy().astype(np.float64)
+        return filter_table(tab, float(seeing), pix, rb=rb, rb_cut=cut), nfound
 
-    def stamps(self, ra, dec, sci, ref, size=63, ref_flxscale=1.0, sci_flxscale=1.0, kernel='LANCZOS3'):
+    def stamps(self, ra, dec, sci, ref, size=63, ref_flxscale=1.0, sci_flxscale=1.0, kernel='LANCZOS3', device_out=False):
         """The thumbnails of the resident difference image (``Engine.stamps``; scripts/dosub.py:133-150): per position
         the stamps of ``self.diff`` and ``sci`` (science grid, resampled onto the reference grid under the stamps only)
         and of the un-aligned ``ref`` (gathered) - the tensors the caller handed to ``run``, which this object does not
         keep.  Enqueued on this chain's stream behind the subtraction; only blocks and norms cross PCIe.
         ``sci_flxscale``: the FLXSCALE card of the science frame and of the difference image (``swarp.run_align``);
         ``ref_flxscale`` is accepted for symmetry with ``run`` (a gathered plane is not scaled).
-        Returns (blocks[n, 3, S, S] in the order sub, new, ref, norms[n, 3], x0, y0)."""
+        Returns (blocks[n, 3, S, S] in the order sub, new, ref, norms[n, 3], x0, y0); with ``device_out`` blocks and norms
+        stay in HBM (``Engine.stamps``)."""
         self.result()
         fs = self.engine.flux_scale(self.wsci, self.wref, float(sci_flxscale))
         self.engine.set_stream(self.stream.cuda_stream)
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))
         planes = [dict(img=self.diff, wcs=self.wsci, fscale=fs), dict(img=sci.contiguous(), wcs=self.wsci, fscale=fs),
                   dict(img=ref.contiguous(), wcs=self.wref, on_grid=True)]
-        return self.engine.stamps(planes, self.wref, ra, dec, size=size, kernel=kernel, stream=self.stream)
+        return self.engine.stamps(planes, self.wref, ra, dec, size=size, kernel=kernel, stream=self.stream,
+                                  device_out=device_out)
 
     def release_overlap(self):
         """Give the second context of ``overlap=True`` back (it is made again on the next run that wants it)."""

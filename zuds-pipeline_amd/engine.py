@@ -72,6 +72,8 @@ class Engine(object):
 
     def close(self):
         if self._ctx:
+            for _, h in self.__dict__.pop('_rb_handles', {}).values():     # realbogus.RBModel.handle
+                self.L.zm_rb_model_destroy(h)
             self.L.zm_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()
 

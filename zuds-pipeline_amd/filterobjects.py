@@ -11,18 +11,21 @@ positions (``X_IMAGE``, ``Y_IMAGE``: 1-based, as SExtractor reports them) by ``p
   +5 sigma, sigma = 1.48 x MAD of the image about its median (``filterobjects.py:155-162``).
 
 ``filter_sexcat(cat)`` is the whole filter on a ``PipelineFITSCatalog``: the column cuts in the reference's order,
-then the pixel cuts.  The braai CNN score is not computed: ``rb`` is -99 for every row, as the reference leaves it
-for rows that never reach the network.
+then the pixel cuts.  Without a model the braai CNN score is not computed: ``rb`` is -99 for every row, as the
+reference leaves it for rows that never reach the network.  ``filter_sexcat(cat, rb_model=m)`` (``realbogus.load_model``)
+scores the rows that survive the pixel cuts (``csrc/braai.hip``) and drops those with ``rb < RB_CUT[image.fid]``
+(``zuds/filterobjects.py:196-240``).
 """
 import ctypes as C
 
 import numpy as np
 
 from ._lib import check, ptr
-from .constants import BAD_SUM
+from .constants import BAD_SUM, RB_CUT
 from .engine import get_engine
 
-__all__ = ['pixel_cuts', 'pixel_cuts_dev', 'column_cuts', 'filter_table', 'filter_sexcat', 'CUTSIZE']
+__all__ = ['pixel_cuts', 'pixel_cuts_dev', 'column_cuts', 'filter_table', 'filter_sexcat', 'CUTSIZE', 'good_before_ml',
+           'rb_cut_for']
 
 CUTSIZE = 11          # pixels, zuds/filterobjects.py:12
 CUT_RADIUS = 6.0      # zuds/filterobjects.py:102-104
@@ -126,10 +129,23 @@ def _append_columns(table, **cols):
     return out.view(np.recarray)
 
 
-def filter_sexcat(cat, engine=None, quiet=False):
+def rb_cut_for(fid=None, rb_cut=None):
+    """The real / bogus threshold: ``rb_cut`` when given, else ``RB_CUT[fid]`` (``zuds/constants.py:18-21``).  Neither:
+    ``ValueError`` - the cut differs between filters and is not guessed."""
+    if rb_cut is not None:
+        return float(rb_cut)
+    try:
+        return float(RB_CUT[int(fid)])
+    except (TypeError, ValueError, KeyError):
+        raise ValueError(f'no real / bogus cut: filter id {fid!r} is not one of {sorted(RB_CUT)} and no rb_cut is given')
+
+
+def filter_sexcat(cat, engine=None, quiet=False, rb_model=None, rb_cut=None):
     """Filter the catalog of a subtraction (``zuds/filterobjects.py:57-246``): adds ``GOODCUT``, ``BPMCUT``,
-    ``RMSCUT`` and ``rb`` (-99: the CNN step is skipped) columns and saves the catalog.  A catalog that already has a
-    ``GOODCUT`` column is returned as it is."""
+    ``RMSCUT`` and ``rb`` columns and saves the catalog.  A catalog that already has a ``GOODCUT`` column is returned as
+    it is.  ``rb_model`` (``realbogus.RBModel``): the rows that survive the pixel cuts get their triplets
+    (``thumbnails._subtraction_blocks``: on the device route the blocks stay in HBM) and their score, and are cut at
+    ``rb_cut`` or ``RB_CUT[image.fid]``; without it ``rb`` is -99 (the CNN step is skipped)."""
     say = (lambda *a, **k: None) if quiet else print
     if 'GOODCUT' in cat.data.dtype.names:
         return cat
@@ -143,21 +159,83 @@ def filter_sexcat(cat, engine=None, quiet=False):
         estimate_seeing(image)
     see = image.header['SEEING']
     pix = pixel_cuts(image.data, rms, bpm, table['X_IMAGE'], table['Y_IMAGE'], engine=engine)
-    cat.data = filter_table(table, see, pix, say=say)
+    if rb_model is None:
+        cat.data = filter_table(table, see, pix, say=say)
+    else:
+        cut = rb_cut_for(getattr(image, 'fid', None), rb_cut)
+        rows = table[good_before_ml(table, see, pix) > 0]
+        rb = _score_rows(rows, image, rb_model, engine)
+        cat.data = filter_table(table, see, pix, say=say, rb=rb, rb_cut=cut)
+        cat.rb_version = rb_model.name
     cat.save()
     return cat
 
 
-def filter_table(table, see, pix, say=None):
+def _score_rows(rows, sub, rb_model, engine=None):
+    """rb of the catalog rows ``rows`` of the subtraction ``sub``: their stamps (sub, new, ref on the reference's grid,
+    one engine call per grid) scored by ``rb_model``."""
+    from . import thumbnails
+
+    class _At(object):
+        def __init__(self, ra, dec):
+            self.ra, self.dec = ra, dec
+    if len(rows) == 0:
+        return np.zeros(0)
+    dets = [_At(float(r['X_WORLD']), float(r['Y_WORLD'])) for r in rows]
+    eng = engine or get_engine()
+    per = {}
+    for blocks, norms, _, _, images, _ in thumbnails._subtraction_blocks(dets, sub, rb_model.in_size, device_out=True):
+        for p, (typ, _) in enumerate(images):
+            per[typ] = (blocks[:, p], norms[:, p])
+    order = thumbnails.STAMP_TYPES
+    if isinstance(per[order[0]][0], np.ndarray):
+        blocks = np.stack([per[t][0] for t in order], axis=1)
+        norms = np.stack([per[t][1] for t in order], axis=1)
+        return rb_model.score_blocks(blocks, norms, order=order, engine=eng).astype(np.float64)
+    import torch
+    from . import objdev
+    eng = get_engine()                                    # the engine _subtraction_blocks bound to the I/O stream
+    stream = objdev.get_io().stream
+    with torch.cuda.stream(stream):
+        blocks = torch.stack([per[t][0] for t in order], dim=1).contiguous()
+        norms = torch.stack([per[t][1] for t in order], dim=1).contiguous()
+        rb = rb_model.score_dev(blocks, norms, order=order, engine=eng, stream=stream)
+        out = rb.cpu()
+    stream.synchronize()
+    return out.numpy().astype(np.float64)
+
+
+def good_before_ml(table, see, pix):
+    """``GOODCUT`` behind the column cuts and the negpix cut: the rows the reference hands to the network."""
+    good, _ = column_cuts(table, see, pix['BPMCUT'], pix['RMSCUT'], pix['MEDCUT'])
+    good[pix['NEGPIX'] != 0] = 0
+    return good
+
+
+def filter_table(table, see, pix, say=None, rb=None, rb_cut=None):
     """The filter itself, for any route that has the pixel cuts ``pix`` (``pixel_cuts`` / ``pixel_cuts_dev``) of the
     rows of ``table``: the column cuts in the reference's order, then the negpix cut; returns the table with the
-    ``GOODCUT``, ``BPMCUT``, ``RMSCUT`` and ``rb`` (-99) columns appended.  ``say``: where the reference's count lines
-    go (``filter_sexcat`` prints them)."""
+    ``GOODCUT``, ``BPMCUT``, ``RMSCUT`` and ``rb`` columns appended.  ``say``: where the reference's count lines
+    go (``filter_sexcat`` prints them).  ``rb``: the scores of the rows that still have ``GOODCUT > 0`` behind the negpix
+    cut (``good_before_ml``), in table order - those rows get them, every other row keeps -99 - and ``GOODCUT`` is
+    cleared where ``rb < rb_cut`` (``zuds/filterobjects.py:233-236``; NaN < cut is false: a row whose stamp has a zero
+    norm keeps its ``GOODCUT``, as in the reference).  Without ``rb``: -99 everywhere, no ML cut."""
     say = say or (lambda *a, **k: None)
     good, left = column_cuts(table, see, pix['BPMCUT'], pix['RMSCUT'], pix['MEDCUT'])
     for name, n in left:
         say(f'Number of candidates after {name} cut: ', n)
     good[pix['NEGPIX'] != 0] = 0
     say('Number of candidates after negpix cut: ', int(good.sum()))
-    return _append_columns(table, GOODCUT=good, BPMCUT=pix['BPMCUT'], RMSCUT=pix['RMSCUT'],
-                           rb=np.full(len(table), -99.0))
+    rbcol = np.full(len(table), -99.0)
+    if rb is not None:
+        if rb_cut is None:
+            raise ValueError('filter_table: rb needs rb_cut')
+        rb = np.asarray(rb, dtype=np.float64).ravel()
+        alive = np.flatnonzero(good > 0)
+        if rb.size != alive.size:
+            raise ValueError(f'filter_table: {alive.size} rows reach the network, {rb.size} scores given')
+        rbcol[alive] = rb
+        with np.errstate(invalid='ignore'):
+            good[alive[rb < float(rb_cut)]] = 0
+        say('Number of candidates after ML cut: ', int(good.sum()))
+    return _append_columns(table, GOODCUT=good, BPMCUT=pix['BPMCUT'], RMSCUT=pix['RMSCUT'], rb=rbcol)

@@ -52,12 +52,21 @@ class SubtractionJob(object):
     ``scripts/donightly.py:40``).  ``stamps``: and ``stamps``, the thumbnails of its ``GOODCUT == 1`` rows
     (``DeviceSubtraction.stamps``: dict of blocks [n, 3, S, S], norms, x0, y0, ra, dec); sci optionally ``flxscale``.
     More than ``max_detections`` such rows: no stamps and ``too_many = True`` (the reference's TooManyDetectionsError,
-    raised after the subtraction's files exist: the products are delivered all the same)."""
+    raised after the subtraction's files exist: the products are delivered all the same).
+    ``rb_model`` (``realbogus.RBModel``, with ``detect``): ``cat`` carries the real / bogus score of the rows that reach
+    the network and the ML cut at ``rb_cut`` or ``RB_CUT[fid]``; ``max_detections`` and ``stamps`` then see the rows that
+    survive that cut, as the reference's driver does."""
 
     def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
-                 max_detections=50):
+                 max_detections=50, rb_model=None, fid=None, rb_cut=None):
         if stamps and not detect:
             raise ValueError('stamps needs detect')
+        if rb_model is not None:
+            from .filterobjects import rb_cut_for
+            if not detect:
+                raise ValueError('rb_model needs detect')
+            rb_cut_for(fid, rb_cut)                      # (raises when neither names a cut)
+        self.rb_model, self.fid, self.rb_cut = rb_model, fid, rb_cut
         self.sci, self.ref, self.radec = sci, ref, radec
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag
         self.detect, self.stamps, self.max_detections = bool(detect), bool(stamps), int(max_detections)
@@ -157,8 +166,17 @@ def _detect(ch, job, out):
     sci, ref = job.sci, job.ref
     ch.result()
     try:
-        cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'])
+        rbkw = {}
+        if getattr(job, 'rb_model', None) is not None:
+            rbkw = dict(rb_model=job.rb_model, sci=sci['img'], ref=ref['img'], fid=job.fid, rb_cut=job.rb_cut,
+                        sci_flxscale=float(sci.get('flxscale', 1.0)))
+        cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'], **rbkw)
     except _lib.ZMError as exc:
+        out['cat'], out['detect_error'] = None, str(exc)
+        return
+    except ValueError as exc:                          # with a model: a surviving row whose stamp misses the reference's grid
+        if not rbkw:
+            raise
         out['cat'], out['detect_error'] = None, str(exc)
         return
     out['cat'], out['nfound'] = cat, int(nfound)

@@ -63,12 +63,14 @@ def _is_device(a):
     return not isinstance(a, np.ndarray) and hasattr(a, 'data_ptr')
 
 
-def _engine_stamps(self, planes, wgrid, ra, dec, size=CUTOUT_SIZE, kernel='LANCZOS3', stream=None):
+def _engine_stamps(self, planes, wgrid, ra, dec, size=CUTOUT_SIZE, kernel='LANCZOS3', stream=None, device_out=False):
     """Stamps of ``planes`` around (ra, dec) on the grid ``wgrid``: (blocks[n, P, S, S] float32, norms[n, P] float64,
     x0, y0).  ``planes``: dicts ``{img, wcs, fscale (1.0), on_grid (False)}``; ``img`` float32 [ny, nx] of ``wcs``, all
     numpy arrays (``zm_stamps``: copied in) or all torch tensors on this engine's GPU (``zm_stamps_dev``: read where they
     lie; only blocks and norms cross PCIe).  A plane with ``on_grid`` is gathered, every other one resampled - only the
     tiles the stamps touch.  ``stream``: the torch stream this engine is bound to, when the planes are produced there.
+    ``device_out`` (device planes only): blocks and norms are returned as the device tensors the kernels wrote, enqueued
+    on the stream and not waited for - for work that reads them there (``realbogus.RBModel.score_dev``).
     A position that is not finite or whose stamp misses the grid raises ``ValueError``."""
     size = int(size)
     if not 1 <= size <= _lib.STAMP_MAX:
@@ -101,6 +103,8 @@ def _engine_stamps(self, planes, wgrid, ra, dec, size=CUTOUT_SIZE, kernel='LANCZ
         arr[i].wcs = s
         arr[i].fscale = float(p.get('fscale', 1.0))
         arr[i].on_grid = int(bool(p.get('on_grid', False)))
+    if device_out and not dev[0]:
+        raise ValueError('device_out needs device planes')
     if not dev[0]:
         blocks = np.zeros((n, P, size, size), np.float32)
         norms = np.zeros((n, P), np.float64)
@@ -116,6 +120,8 @@ def _engine_stamps(self, planes, wgrid, ra, dec, size=CUTOUT_SIZE, kernel='LANCZ
         d_norms = torch.empty((n, P), dtype=torch.float64, device=device)
         check(self.L.zm_stamps_dev(self._ctx, P, arr, C.byref(g), kern, n, x0.ctypes.data, y0.ctypes.data, size,
                                    d_blocks.data_ptr(), d_norms.data_ptr()), 'zm_stamps_dev')
+        if device_out:
+            return d_blocks, d_norms, x0, y0
         self.synchronize()
         return d_blocks.cpu().numpy(), d_norms.cpu().numpy(), x0, y0
 
@@ -275,9 +281,10 @@ def _plane_of(img, on_grid, grid):
     return dict(wcs=w, fscale=fs, on_grid=on_grid)
 
 
-def _subtraction_blocks(detections, sub, size):
+def _subtraction_blocks(detections, sub, size, device_out=False):
     """The engine calls behind ``Thumbnail.from_detections`` / ``triplets``: a list of (blocks, norms, x0, y0, [(type,
-    image)], [grid per plane]) - one entry when all planes end on one grid."""
+    image)], [grid per plane]) - one entry when all planes end on one grid.  ``device_out``: on the device route blocks and
+    norms stay in HBM (torch tensors on the I/O stream, not waited for); the host route returns arrays either way."""
     from . import objdev
     from .subtraction import SingleEpochSubtraction
     ref, sci = sub.reference_image, sub.target_image
@@ -310,7 +317,7 @@ def _subtraction_blocks(detections, sub, size):
             eng.set_stream(oio.stream.cuda_stream)
             for p, t in zip(planes, tensors):
                 p['img'] = t.contiguous()
-            blocks, norms, x0, y0 = eng.stamps(planes, grid, ra, dec, size, stream=oio.stream)
+            blocks, norms, x0, y0 = eng.stamps(planes, grid, ra, dec, size, stream=oio.stream, device_out=device_out)
         else:
             for p, (_, im, _) in zip(planes, members):
                 p['img'] = np.ascontiguousarray(im.data, dtype=np.float32)
@@ -342,7 +349,8 @@ def make_triplet_for_braai(ra, dec, new_aligned, ref_aligned, sub_aligned, old_n
 def triplets(detections, sub, size=CUTOUT_SIZE):
     """The triplets of all detections of a subtraction through the engine call of ``Thumbnail.from_detections``:
     [n, size, size, 3] float64, channels new, ref, sub (``make_triplet_for_braai``'s order), each divided by the norm
-    the engine returns.  No network is shipped: ``rb`` stays -99."""
+    the engine returns - the input of ``realbogus.RBModel.score_triplets`` (the filter itself scores the blocks where
+    they lie: ``filter_sexcat(cat, rb_model=...)``)."""
     detections = list(detections)
     out = np.zeros((len(detections), int(size), int(size), 3))
     chan = {'new': 0, 'ref': 1, 'sub': 2}

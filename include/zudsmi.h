@@ -703,6 +703,45 @@ int zm_rb_score_dev(zm_ctx* ctx, const zm_rb_model* model, int n, const float* b
 int zm_rb_score(zm_ctx* ctx, const zm_rb_model* model, int n, const float* blocks, const double* norms,
                 int nplanes, const int32_t* plane_of_channel, float* rb);
 
+/* ---- source association: a night's detections into sources ------------------- */
+/* The join and the clustering of the reference's associate() (nersc/makesources.py:263-456) and the nearest-neighbour
+ * match behind its q3c joins (csrc/associate.hip; DESIGN.md, "Source association").
+ * Positions are degrees.  Two rows are neighbours when the chord between their fp64 unit vectors is <= 2 sin(r / 2)
+ * (inclusive); radius_arcsec must lie in 0.25 .. 3600.  A row whose ra, dec or snr is not finite takes part in nothing.
+ *
+ * zm_associate_dev: connected components of the neighbour graph of n rows, as DBSCAN(eps = r, min_samples = 2) labels them:
+ *   label[n]        -1 for a row without a neighbour, else its source: sources are numbered by the rank of their
+ *                   smallest row index;
+ *   nsrc            one word: the number of sources;
+ *   offsets, members   CSR of the rows of every source, ascending within a source.  offsets has n + 1 entries: entries
+ *                   nsrc .. n all hold the number of rows that belong to a source;
+ *   best[nsrc]      the row of greatest snr (ties: the lowest index);
+ *   count[nsrc]     rows of the source (entries nsrc .. n - 1 are zeroed);
+ *   sumrb[nsrc]     fp64 sum of rb over the members in ascending order (0 when rb is NULL): the same bits on every run.
+ * Every array is device memory with room for n entries (offsets: n + 1); rb_dev may be NULL.  Enqueued on the context's
+ * stream; the call waits for the verdict of every propagation round (a device word per round), not for the compaction
+ * behind the last one.  n = 0: nsrc = 0 and offsets[0] = 0 are enqueued, nothing else is touched. */
+int zm_associate_dev(zm_ctx* ctx, int n, const double* ra_dev, const double* dec_dev, const double* snr_dev,
+                     const double* rb_dev, double radius_arcsec, int32_t* label_dev, int32_t* nsrc_dev,
+                     int32_t* offsets_dev, int32_t* members_dev, int32_t* best_dev, int32_t* count_dev, double* sumrb_dev);
+/* the same on host arrays of the same sizes: copied in, the call waits; only the first nsrc (offsets: nsrc + 1, members:
+ * offsets[nsrc]) entries of the per-source arrays are written */
+int zm_associate(zm_ctx* ctx, int n, const double* ra, const double* dec, const double* snr, const double* rb,
+                 double radius_arcsec, int32_t* label, int32_t* nsrc, int32_t* offsets, int32_t* members, int32_t* best,
+                 int32_t* count, double* sumrb);
+/* For each of n positions the nearest of m catalogue positions within the radius (ties: the lowest catalogue index):
+ * idx[n] (-1: none) and sep[n] in arcsec (NaN: none).  A position that is not finite matches nothing, a catalogue row that
+ * is not finite is matched by nothing.  Device memory, enqueued on the context's stream, nothing waited for.  n = 0:
+ * nothing happens; m = 0: every idx is -1. */
+int zm_crossmatch_dev(zm_ctx* ctx, int n, const double* ra_dev, const double* dec_dev, int m, const double* cat_ra_dev,
+                      const double* cat_dec_dev, double radius_arcsec, int32_t* idx_dev, double* sep_dev);
+/* the same on host arrays: copied in, the call waits */
+int zm_crossmatch(zm_ctx* ctx, int n, const double* ra, const double* dec, int m, const double* cat_ra,
+                  const double* cat_dec, double radius_arcsec, int32_t* idx, double* sep);
+/* What the last of the four calls above did on this context (waits for the stream): out4 = propagation rounds (0 for a
+ * cross-match), slots of the cell table, probes summed over every insertion, the longest probe of one insertion. */
+int zm_assoc_stats(zm_ctx* ctx, int64_t* out4);
+
 /* ---- FITS data blocks on the device ------------------------------------------ */
 /* Replaces the host-side decode / encode astropy does inside FITSFile.load_data / save
  * (zuds/fitsfile.py:69-94,146-206): raw_dev holds the big-endian data block of a primary

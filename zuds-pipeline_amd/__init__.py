@@ -29,6 +29,7 @@ from .catalog import *
 from .detections import *
 from .thumbnails import *
 from .realbogus import *
+from .source import *
 from . import synth, fits
 
 # same DB-free entry points as the reference

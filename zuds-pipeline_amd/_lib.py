@@ -271,6 +271,11 @@ _SIGS = {
     'zm_rb_model_destroy': (C.c_int, [_P]),
     'zm_rb_score_dev': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
     'zm_rb_score': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    'zm_associate_dev': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    'zm_associate': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    'zm_crossmatch_dev': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P]),
+    'zm_crossmatch': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P]),
+    'zm_assoc_stats': (C.c_int, [_P, _P]),
     'zm_timing_enable': (C.c_int, [_P, C.c_int]),
     'zm_timing_filter': (C.c_int, [_P, C.c_char_p]),
     'zm_timing_reset': (C.c_int, [_P]),

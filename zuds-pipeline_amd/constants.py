@@ -43,3 +43,9 @@ REFERENCE_VERSION = 'zuds5'
 # the real / bogus cut of the candidate filter (zuds/constants.py:18-21): per filter id, and the model it was set for
 RB_CUT = {1: 0.3, 2: 0.3, 3: 0.6}
 BRAAI_MODEL = 'braai_d6_m9'
+
+# source association (nersc/makesources.py:24,33,150-155): the real / bogus score a detection needs to seed a source, the
+# radius that links detections (and a detection to a known source), the radius inside which a star vetoes a source
+ASSOC_RB_MIN = 0.4
+ASSOC_RADIUS_ARCSEC = 2.0
+STAR_VETO_ARCSEC = 1.5

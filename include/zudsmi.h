@@ -742,6 +742,54 @@ int zm_crossmatch(zm_ctx* ctx, int n, const double* ra, const double* dec, int m
  * cross-match), slots of the cell table, probes summed over every insertion, the longest probe of one insertion. */
 int zm_assoc_stats(zm_ctx* ctx, int64_t* out4);
 
+/* ---- astrometric refit: detections against a star catalogue -> the PV terms of a TPV header ---- */
+/* Stands where the reference runs SCAMP (zuds/scamp.py:16-113, astromatic/default.scamp); the operator is stated in
+ * DESIGN.md, "Astrometric refit" (csrc/astrometry.hip): a vote for the gross offset (MATCH Y, POSITION_MAXERR), then rounds
+ * of cross-identification (zm_crossmatch_dev at CROSSID_RADIUS) and a clipped weighted polynomial fit per axis.  CRPIX, CRVAL
+ * and CD never change: the solution lives in PVi_0 .. PVi_10 (no radial terms).  SCAMP's own digits are not claimed. */
+typedef struct zm_astrom_params {
+    double position_maxerr;   /* P, arcsec: half width of the vote's window                          (60)  */
+    double match_resol;       /* q, arcsec: the vote's bin; 0 = crossid_radius / 2                   (0)   */
+    double crossid_radius;    /* arcsec, inclusive                                                   (2)   */
+    double clip_nsigma;       /* a row stays while chi2 <= 2 clip_nsigma^2 max(1, reduced chi2)      (3)   */
+    int32_t degree;           /* 1, 2 or 3: 3, 6 or 10 coefficients per axis                         (3)   */
+    int32_t match;            /* 0 skips the vote                                                    (1)   */
+    int32_t match_nmax;       /* detections of greatest snr that vote                                (1024)*/
+    int32_t max_rounds;       /* cross-id + fit rounds                                               (8)   */
+    int32_t max_clip;         /* fits per round                                                      (10)  */
+    int32_t pad_;
+} zm_astrom_params;
+void zm_astrom_params_default(zm_astrom_params* p);
+
+enum { ZM_ASTROM_OK = 0, ZM_ASTROM_TOO_FEW = 1, ZM_ASTROM_AMBIGUOUS = 2, ZM_ASTROM_SINGULAR = 3,
+       ZM_ASTROM_NOT_CONVERGED = 4 };
+
+typedef struct zm_astrom_result {
+    zm_wcs wcs;               /* the solution (TPV); the input header unless status is OK or NOT_CONVERGED */
+    double shift[2];          /* the vote's offset (xi, eta), arcsec, star - detection                      */
+    double rms[2];            /* unweighted rms residual of the rows used, per axis, arcsec (ASTRRMS1 / 2)  */
+    double chi2;              /* sum of chi2 over the rows used                                             */
+    int32_t status;
+    int32_t vote_peak, vote_runner_up;
+    int32_t nmatch, nused, rounds;
+} zm_astrom_result;
+
+/* nframes frames against one catalogue of m stars.  Rows of all frames are concatenated: frame f owns rows
+ * offsets[f] .. offsets[f + 1] - 1 of x, y (FITS 1-based pixels), sd (position sigma, pixels), snr (rank key), match
+ * (index of the star a row is identified with, or -1) and used (1: the row was in the last fit).  ref_ra, ref_dec are
+ * degrees, ref_sig arcsec.  A row with a value that is not finite takes part in nothing.  Detection, star, match and used
+ * arrays are device memory; wcs0, offsets and results are host memory.  The call waits for one word per frame after the
+ * vote and after every round; two calls on the same input give the same bits.  nframes <= 65535. */
+int zm_astrom_solve_dev(zm_ctx* ctx, int nframes, const zm_wcs* wcs0, const int32_t* offsets, const double* x_dev,
+                        const double* y_dev, const double* sd_dev, const double* snr_dev, int m, const double* ref_ra_dev,
+                        const double* ref_dec_dev, const double* ref_sig_dev, const zm_astrom_params* params,
+                        zm_astrom_result* results, int32_t* match_dev, uint8_t* used_dev);
+/* the same on host arrays: copied in, the call waits; the same bits as the device form */
+int zm_astrom_solve(zm_ctx* ctx, int nframes, const zm_wcs* wcs0, const int32_t* offsets, const double* x, const double* y,
+                    const double* sd, const double* snr, int m, const double* ref_ra, const double* ref_dec,
+                    const double* ref_sig, const zm_astrom_params* params, zm_astrom_result* results, int32_t* match,
+                    uint8_t* used);
+
 /* ---- FITS data blocks on the device ------------------------------------------ */
 /* Replaces the host-side decode / encode astropy does inside FITSFile.load_data / save
  * (zuds/fitsfile.py:69-94,146-206): raw_dev holds the big-endian data block of a primary

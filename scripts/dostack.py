@@ -9,6 +9,11 @@ queries replaced by a job file: every row of ``jobs.csv`` has ``target`` (scienc
 image paths joined by ';' -- each with its ``*mskimg.fits`` beside it) and the
 bin edges ``left`` / ``right`` that go into the coadd's file name.  A job whose
 output already exists is skipped, which is how an interrupted run resumes.
+
+    dostack.py jobs.csv --solve-astrometry --astref stars.cat [--distort-degrees N]
+
+refits the astrometry of the inputs and of the coadd against the FITS_LDAC star catalogue ``stars.cat``
+(``from_images(solve_astrometry=True)``; the reference's SCAMP step, ``zuds/coadd.py:120-123,219-223``).
 """
 import argparse
 import os
@@ -40,7 +45,7 @@ def coadd_name(first, left, right):
     return os.path.join(os.path.dirname(first.local_path), stem + '.coadd.fits')
 
 
-def run_job(job, tmpdir):
+def run_job(job, tmpdir, scamp_kws=None):
     t0 = time.time()
     images = load_inputs(job['target'])
     outname = coadd_name(images[0], job['left'], job['right'])
@@ -51,7 +56,8 @@ def run_job(job, tmpdir):
     try:
         stack = zuds.ScienceCoadd.from_images(images, outfile_name=outname,
                                               data_product=False, tmpdir=tmpdir,
-                                              nthreads=zuds.get_nthreads())
+                                              nthreads=zuds.get_nthreads(),
+                                              solve_astrometry=scamp_kws is not None, scamp_kws=scamp_kws)
     except Exception as exc:        # one bad job must not end the night's run
         print(exc, [im.basename for im in images], flush=True)
         return None
@@ -70,12 +76,20 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('jobs')
     ap.add_argument('--tmpdir', default='/tmp')
+    ap.add_argument('--solve-astrometry', action='store_true', help='refit the astrometry of the inputs and of the coadd')
+    ap.add_argument('--astref', help='FITS_LDAC star catalogue (ASTREF_CATALOG FILE, ASTREFCAT_NAME)')
+    ap.add_argument('--distort-degrees', type=int, default=3, help='degree of the distortion polynomial (1, 2 or 3)')
     args = ap.parse_args(argv)
+    scamp_kws = None
+    if args.solve_astrometry:
+        if not args.astref:
+            ap.error('--solve-astrometry needs --astref FILE')
+        scamp_kws = {'ASTREF_CATALOG': 'FILE', 'ASTREFCAT_NAME': args.astref, 'DISTORT_DEGREES': args.distort_degrees}
     zuds.init_db()
     share = zuds.get_my_share_of_work(args.jobs, reader=pd.read_csv)
     table = share if isinstance(share, pd.DataFrame) else pd.DataFrame(list(share))
     for _, row in table.iterrows():
-        run_job(row, args.tmpdir)
+        run_job(row, args.tmpdir, scamp_kws)
     return 0
 
 

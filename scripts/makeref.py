@@ -2,7 +2,7 @@
 """Make the reference images: the driver of the reference's ``scripts/makeref.py``,
 database-free.
 
-usage: makeref.py dirs.txt min_date max_date version
+usage: makeref.py dirs.txt min_date max_date version [--solve-astrometry --astref FILE [--distort-degrees N]]
 
 ``dirs.txt`` lists directories; each is searched for ``ztf*sciimg.fits`` (masks as
 ``*mskimg.fits`` beside them).  The selection is the reference's
@@ -14,6 +14,9 @@ usage: makeref.py dirs.txt min_date max_date version
 is written into the directory by ``ReferenceImage.from_images`` - one ``zm_coadd`` call where
 the reference ran SWarp twice.  A directory whose reference exists is skipped (resume by name).
 The reference's catalog / archive / database steps that follow are out of scope here.
+
+``--solve-astrometry --astref FILE``: refit the astrometry of the inputs and of the reference against the FITS_LDAC
+star catalogue FILE (``from_images(solve_astrometry=True)``; ``--distort-degrees`` 1, 2 or 3, default 3).
 """
 import os
 import sys
@@ -71,7 +74,7 @@ def select(directory, min_date, max_date):
     return sorted(ok, key=lambda i: float(i.header['MAGLIM']), reverse=True)[:MAX_FRAMES]
 
 
-def make_one(directory, min_date, max_date, version, tmpdir='./tmp'):
+def make_one(directory, min_date, max_date, version, tmpdir='./tmp', scamp_kws=None):
     t_start = time.time()
     top = select(directory, min_date, max_date)
     if len(top) == 0:
@@ -90,9 +93,15 @@ def make_one(directory, min_date, max_date, version, tmpdir='./tmp'):
         return None
     try:
         coadd = zuds.ReferenceImage.from_images(top, coaddname, data_product=True,
-                                                nthreads=zuds.get_nthreads(), tmpdir=tmpdir)
+                                                nthreads=zuds.get_nthreads(), tmpdir=tmpdir,
+                                                solve_astrometry=scamp_kws is not None, scamp_kws=scamp_kws)
         coadd.version = version
     except TypeError as e:
+        print(e, [t.basename for t in top], coaddname)
+        return None
+    except RuntimeError as e:       # a frame whose astrometric refit failed: this directory is skipped, the run goes on
+        if scamp_kws is None:
+            raise
         print(e, [t.basename for t in top], coaddname)
         return None
     t_stop = time.time()
@@ -100,8 +109,34 @@ def make_one(directory, min_date, max_date, version, tmpdir='./tmp'):
     return coadd
 
 
+def astrometry_options(argv):
+    """(argv without the astrometry options, scamp_kws or None)."""
+    solve, astref, degree, rest = False, None, 3, []
+    it = iter(argv)
+    for a in it:
+        if a == '--solve-astrometry':
+            solve = True
+        elif a in ('--astref', '--distort-degrees'):
+            value = next(it, None)
+            if value is None or value.startswith('--'):
+                sys.exit(f'{a} needs a value')
+            if a == '--astref':
+                astref = value
+            else:
+                degree = int(value)
+        else:
+            rest.append(a)
+    if not solve:
+        if astref is not None:
+            sys.exit('--astref is only read with --solve-astrometry')
+        return rest, None
+    if not astref:
+        sys.exit('--solve-astrometry needs --astref FILE')
+    return rest, {'ASTREF_CATALOG': 'FILE', 'ASTREFCAT_NAME': astref, 'DISTORT_DEGREES': degree}
+
+
 def main(argv=None):
-    argv = sys.argv[1:] if argv is None else argv
+    argv, scamp_kws = astrometry_options(list(sys.argv[1:] if argv is None else argv))
     if len(argv) != 4:
         sys.exit(__doc__)
     infile, version = argv[0], argv[3]
@@ -109,7 +144,7 @@ def main(argv=None):
     zuds.init_db()
     made = []
     for d in zuds.get_my_share_of_work(infile):
-        coadd = make_one(str(d), min_date, max_date, version)
+        coadd = make_one(str(d), min_date, max_date, version, scamp_kws=scamp_kws)
         if coadd is not None:
             made.append(coadd.local_path)
     return made

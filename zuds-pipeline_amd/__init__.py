@@ -30,7 +30,8 @@ from .detections import *
 from .thumbnails import *
 from .realbogus import *
 from .source import *
-from . import synth, fits
+from .scamp import *
+from . import synth, fits, scamp
 
 # same DB-free entry points as the reference
 def init_db(*args, **kwargs):

@@ -144,6 +144,20 @@ class zm_rb_layer(C.Structure):
                 ('w_off', C.c_int64), ('b_off', C.c_int64)]
 
 
+class zm_astrom_params(C.Structure):
+    _fields_ = [('position_maxerr', C.c_double), ('match_resol', C.c_double), ('crossid_radius', C.c_double),
+                ('clip_nsigma', C.c_double), ('degree', C.c_int32), ('match', C.c_int32), ('match_nmax', C.c_int32),
+                ('max_rounds', C.c_int32), ('max_clip', C.c_int32), ('pad_', C.c_int32)]
+
+
+class zm_astrom_result(C.Structure):
+    """One frame of ``zm_astrom_solve`` (include/zudsmi.h)."""
+    _fields_ = [('wcs', zm_wcs), ('shift', C.c_double * 2), ('rms', C.c_double * 2), ('chi2', C.c_double),
+                ('status', C.c_int32), ('vote_peak', C.c_int32), ('vote_runner_up', C.c_int32),
+                ('nmatch', C.c_int32), ('nused', C.c_int32), ('rounds', C.c_int32)]
+
+
+ASTROM_STATUS = ('OK', 'TOO_FEW', 'AMBIGUOUS', 'SINGULAR', 'NOT_CONVERGED')      # ZM_ASTROM_*
 RB_CHUNK = 128                                         # ZM_RB_CHUNK
 RB_CONV2D, RB_MAXPOOL, RB_FLATTEN, RB_DENSE = 1, 2, 3, 4
 RB_ACTIVATION = {'linear': 0, 'relu': 1, 'sigmoid': 2}
@@ -276,6 +290,11 @@ _SIGS = {
     'zm_crossmatch_dev': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P]),
     'zm_crossmatch': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P]),
     'zm_assoc_stats': (C.c_int, [_P, _P]),
+    'zm_astrom_params_default': (None, [C.POINTER(zm_astrom_params)]),
+    'zm_astrom_solve_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_wcs), _P, _P, _P, _P, _P, C.c_int, _P, _P, _P,
+                                      C.POINTER(zm_astrom_params), C.POINTER(zm_astrom_result), _P, _P]),
+    'zm_astrom_solve': (C.c_int, [_P, C.c_int, C.POINTER(zm_wcs), _P, _P, _P, _P, _P, C.c_int, _P, _P, _P,
+                                  C.POINTER(zm_astrom_params), C.POINTER(zm_astrom_result), _P, _P]),
     'zm_timing_enable': (C.c_int, [_P, C.c_int]),
     'zm_timing_filter': (C.c_int, [_P, C.c_char_p]),
     'zm_timing_reset': (C.c_int, [_P]),

@@ -38,11 +38,14 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
     if outname is None:
         raise TypeError('from_images() missing required argument: "outname"')
     outname = str(outname)
-    images = np.atleast_1d(images)
+    images = inputs = np.atleast_1d(images)
     mskoutname = outname.replace('.fits', '.mask.fits')
     if solve_astrometry:
-        raise NotImplementedError('solve_astrometry needs SCAMP (zuds/scamp.py), which is '
-                                  'outside the coadd / subtraction path')
+        # transaction copies (zuds/coadd.py:77-118): shallow copies with header dicts of their own, so that the
+        # caller's objects and files stay as they are
+        from .scamp import transaction_copies
+        images = np.empty(len(inputs), dtype=object)
+        images[:] = transaction_copies(list(inputs))
     if enforce_partition:
         # make sure all images have the same field, filter, ccdid, qid:
         ensure_images_have_the_same_properties(images, GROUP_PROPERTIES)
@@ -58,6 +61,11 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
     # files; buffers are handed over in memory here, only the call objects keep
     # the directory name for their legacy command strings
     directory = Path(tmpdir) / uuid.uuid4().hex
+    if solve_astrometry:
+        # zuds/coadd.py:120-123: the inputs are solved first, and the solved cards go into the copies' header dicts (the
+        # `.head` files SCAMP leaves for SWarp).  Everything below takes the frames' WCS from `im.wcs` of the copies.
+        from .scamp import solve_into
+        solve_into(list(images), scamp_kws)
     sci = prepare_swarp_sci(list(images), outname, directory, swarp_kws=sci_swarp_kws,
                             swarp_zp_key=swarp_zp_key)
     masks = [image.mask_image for image in images]
@@ -74,8 +82,12 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
     from . import objdev
     if objdev.enabled():
         # the device route: raw FITS blocks -> HBM -> kernels -> encoded products, every file written once
-        return _coadd_device(cls, images, masks, sci, params, outname, mskoutname, addbkg, enforce_partition,
-                             set_date, calculate_seeing, data_product)
+        coadd = _coadd_device(cls, images, masks, sci, params, outname, mskoutname, addbkg, enforce_partition,
+                              set_date, calculate_seeing, data_product)
+        coadd.input_images = inputs.tolist()
+        if solve_astrometry:
+            _solve_coadd(coadd, scamp_kws, tmpdir)
+        return coadd
 
     # one fused device pass: science frames and their masks share the lattice
     eng = get_engine()
@@ -104,7 +116,7 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
     coaddmask.update_from_weight_map(coaddmaskweight)   # bit 16, zuds/coadd.py:182-184
 
     # keep a record of the images that went into the coadd
-    coadd.input_images = images.tolist()
+    coadd.input_images = inputs.tolist()
     coadd.mask_image = coaddmask
     coaddmask.parent_image = coadd
     if enforce_partition:
@@ -119,6 +131,8 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
         coadd.header_comments['MJD-OBS'] = 'Median MJD of the coadd inputs (DG)'
     coadd.save()
     coaddmask.save()
+    if solve_astrometry:
+        _solve_coadd(coadd, scamp_kws, tmpdir)
     if calculate_seeing:
         # zuds/coadd.py:225-226; the stars come from the pixels instead of a Gaia match
         # (seeing.py).  A coadd without a usable star keeps the inputs' median FWHM.
@@ -134,6 +148,16 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
     if data_product:
         warnings.warn('data_product=True: archiving is not part of this package')
     return coadd
+
+
+def _solve_coadd(coadd, scamp_kws, tmpdir):
+    """``zuds/coadd.py:219-223``: the coadd itself is solved in place and its catalog remade under the new header."""
+    from .catalog import PipelineFITSCatalog
+    from .scamp import calibrate_astrometry
+    # what the refit found is kept on the object: `shift` is how far the coadd's own header was from the catalogue
+    # before the refit - a vote bin or less when the inputs went in with solved headers
+    coadd.astrometry_info = calibrate_astrometry([coadd], inplace=True, scamp_kws=scamp_kws, tmpdir=tmpdir)[0]
+    coadd.catalog = PipelineFITSCatalog.from_image(coadd, columns='param')
 
 
 def _coadd_device(cls, images, masks, sci, params, outname, mskoutname, addbkg, enforce_partition, set_date,

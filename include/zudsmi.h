@@ -315,7 +315,8 @@ int zm_coadd_finalize_dev(zm_ctx* ctx, float* s1_to_img, const float* s0,
  * another partial mask in (AND / OR over the covering frames, -1 = identity; first != 0
  * initialises acc from m), zm_mask_finalize_dev turns the marker into 0 and writes the
  * coverage plane (cov may be NULL) - the mask SWarp run of zuds/swarp.py:83-104 sharded
- * by frame. */
+ * by frame.  -1 is the marker and nothing else: a real mask value of -1 (all 32 bits set), in m or
+ * as the OR of covering frames, cannot be told from "not covered" and is folded as such. */
 int zm_mask_accum_dev(zm_ctx* ctx, int32_t* acc, const int32_t* m, int64_t npix,
                       int kind, int first);
 int zm_mask_finalize_dev(zm_ctx* ctx, int32_t* acc, float* cov, int64_t npix);

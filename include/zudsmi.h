@@ -743,6 +743,50 @@ int zm_crossmatch(zm_ctx* ctx, int n, const double* ra, const double* dec, int m
  * cross-match), slots of the cell table, probes summed over every insertion, the longest probe of one insertion. */
 int zm_assoc_stats(zm_ctx* ctx, int64_t* out4);
 
+/* ---- light curves: footprint join and batched forced photometry --------------- */
+/* The per-subtraction loop of the reference's scripts/dophot.py - q3c_poly_query(Source.ra, Source.dec,
+ * wcs.calc_footprint()) and raw_aperture_photometry at the positions it returns - for many images at once
+ * (csrc/lightcurve.hip; DESIGN.md, "Light curves").
+ *
+ * Footprint of an image: the spherical quadrilateral whose vertices are the sky positions of the centres of its four
+ * corner pixels ((1, 1), (1, NAXIS2), (NAXIS1, NAXIS2), (NAXIS1, 1): WCS.calc_footprint, center = True), joined by great
+ * circles.  A source is inside when its unit vector is on the inner side of all four edge planes (boundary inclusive) and
+ * in the hemisphere of the vertex sum; the inner side follows from the polygon's own orientation (det(CD) of either sign).
+ * A polygon that is degenerate or not convex is an error.  A source whose ra or dec is not finite joins nothing.
+ *
+ * zm_footprint_join_dev: wcs[nimg] is host memory, ra / dec[nsrc] (degrees) device memory.
+ *   offsets[nimg + 1]   int64, device: the pairs of image i are entries offsets[i] .. offsets[i + 1] - 1 of src_idx;
+ *                       always complete, offsets[nimg] is the number of pairs whatever the capacity;
+ *   src_idx[capacity]   int32, device: source indices, ascending within an image; the same bytes on every run;
+ *   *out_npairs         host: the number of pairs.  When it exceeds `capacity`, only the first `capacity` entries of src_idx
+ *                       were written and nothing past them (the zm_find_stars contract): call again with room for all.
+ * The call waits for that one word.  nimg <= 65535, nsrc <= 2^30. */
+int zm_footprint_join_dev(zm_ctx* ctx, int nimg, const zm_wcs* wcs, int nsrc, const double* ra_dev, const double* dec_dev,
+                          int64_t capacity, int64_t* offsets_dev, int32_t* src_idx_dev, int64_t* out_npairs);
+/* the same on host arrays: copied in, the call waits; min(*out_npairs, capacity) entries of src_idx are written */
+int zm_footprint_join(zm_ctx* ctx, int nimg, const zm_wcs* wcs, int nsrc, const double* ra, const double* dec,
+                      int64_t capacity, int64_t* offsets, int32_t* src_idx, int64_t* out_npairs);
+
+typedef struct zm_lc_image {
+    const float* img;       /* device, ny x nx */
+    const float* rms;       /* device or NULL */
+    const int32_t* mask;    /* device or NULL */
+    zm_wcs wcs;
+    int32_t nx, ny;
+} zm_lc_image;
+
+/* Forced photometry of every pair of a join in one launch, one wave per pair: the source goes through its image's WCS on
+ * the device (TPV inverse included), then the aperture is summed exactly as zm_aperture_photometry_dev sums it - flux, err
+ * and flags are the bits that call returns at (x, y).  images[nimg] is host memory (its pointers device memory; sizes may
+ * differ from image to image); offsets / src_idx are a join's (npairs <= offsets[nimg]: a clipped list is fine), ra / dec
+ * [nsrc] the positions it was made from.  Per pair, device memory: x, y (0-based pixels), flux, err (fp64), flags (int32).
+ * A src_idx entry outside 0 .. nsrc - 1 gives NaN positions and zero sums.  Enqueued on the context's stream, nothing waited
+ * for (the image table is copied from pinned memory the next call leaves alone until that copy is done). */
+int zm_forced_photometry_batch_dev(zm_ctx* ctx, int nimg, const zm_lc_image* images, const int64_t* offsets_dev,
+                                   const int32_t* src_idx_dev, int64_t npairs, int nsrc, const double* ra_dev,
+                                   const double* dec_dev, double radius, double* x_dev, double* y_dev, double* flux_dev,
+                                   double* err_dev, int32_t* flags_dev);
+
 /* ---- astrometric refit: detections against a star catalogue -> the PV terms of a TPV header ---- */
 /* Stands where the reference runs SCAMP (zuds/scamp.py:16-113, astromatic/default.scamp); the operator is stated in
  * DESIGN.md, "Astrometric refit" (csrc/astrometry.hip): a vote for the gross offset (MATCH Y, POSITION_MAXERR), then rounds

@@ -30,8 +30,9 @@ from .detections import *
 from .thumbnails import *
 from .realbogus import *
 from .source import *
+from .lightcurve import *
 from .scamp import *
-from . import synth, fits, scamp
+from . import synth, fits, scamp, lightcurve
 
 # same DB-free entry points as the reference
 def init_db(*args, **kwargs):

@@ -157,6 +157,12 @@ class zm_astrom_result(C.Structure):
                 ('nmatch', C.c_int32), ('nused', C.c_int32), ('rounds', C.c_int32)]
 
 
+class zm_lc_image(C.Structure):
+    """One image of ``zm_forced_photometry_batch_dev`` (include/zudsmi.h): device pointers, WCS and sizes."""
+    _fields_ = [('img', C.c_void_p), ('rms', C.c_void_p), ('mask', C.c_void_p), ('wcs', zm_wcs),
+                ('nx', C.c_int32), ('ny', C.c_int32)]
+
+
 ASTROM_STATUS = ('OK', 'TOO_FEW', 'AMBIGUOUS', 'SINGULAR', 'NOT_CONVERGED')      # ZM_ASTROM_*
 RB_CHUNK = 128                                         # ZM_RB_CHUNK
 RB_CONV2D, RB_MAXPOOL, RB_FLATTEN, RB_DENSE = 1, 2, 3, 4
@@ -290,6 +296,12 @@ _SIGS = {
     'zm_crossmatch_dev': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P]),
     'zm_crossmatch': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P, C.c_double, _P, _P]),
     'zm_assoc_stats': (C.c_int, [_P, _P]),
+    'zm_footprint_join_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_wcs), C.c_int, _P, _P, C.c_int64, _P, _P,
+                                        C.POINTER(C.c_int64)]),
+    'zm_footprint_join': (C.c_int, [_P, C.c_int, C.POINTER(zm_wcs), C.c_int, _P, _P, C.c_int64, _P, _P,
+                                    C.POINTER(C.c_int64)]),
+    'zm_forced_photometry_batch_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_lc_image), _P, _P, C.c_int64, C.c_int, _P, _P,
+                                                 C.c_double, _P, _P, _P, _P, _P]),
     'zm_astrom_params_default': (None, [C.POINTER(zm_astrom_params)]),
     'zm_astrom_solve_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_wcs), _P, _P, _P, _P, _P, C.c_int, _P, _P, _P,
                                       C.POINTER(zm_astrom_params), C.POINTER(zm_astrom_result), _P, _P]),

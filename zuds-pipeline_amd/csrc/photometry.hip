@@ -16,42 +16,12 @@ __global__ __launch_bounds__(64) void k_aperture(const float* __restrict__ img,
                                                  int32_t* __restrict__ flags) {
     const int k = blockIdx.x, lane = threadIdx.x;
     if (k >= npos) return;
-    const double xc = xs[k], yc = ys[k];
-    int ixmin = 0, ixmax = 0, iymin = 0, iymax = 0;
-    if (isfinite(xc) && isfinite(yc)) {
-        // photutils BoundingBox.from_float(x - r, x + r, y - r, y + r), clipped to the frame.  The bounds are
-        // clamped to [-1, n + 1] while still double: a double outside int's range has no defined conversion
-        ixmin = max((int)fmin(fmax(floor(xc - r + 0.5), -1.0), nx + 1.0), 0);
-        ixmax = min((int)fmin(fmax(ceil(xc + r + 0.5), -1.0), nx + 1.0), nx);
-        iymin = max((int)fmin(fmax(floor(yc - r + 0.5), -1.0), ny + 1.0), 0);
-        iymax = min((int)fmin(fmax(ceil(yc + r + 0.5), -1.0), ny + 1.0), ny);
-    }
-    const int bw = ixmax - ixmin, bh = iymax - iymin;
-    double f = 0.0, v = 0.0;
-    int fl = 0;
-    if (bw > 0 && bh > 0) {
-        for (int e = lane; e < bw * bh; e += 64) {
-            const int j = iymin + e / bw, i = ixmin + e % bw;
-            const double x0 = i - 0.5 - xc, x1 = i + 0.5 - xc, y0 = j - 0.5 - yc, y1 = j + 0.5 - yc;
-            const double frac = ap_signed(x1, y1, r) - ap_signed(x0, y1, r) - ap_signed(x1, y0, r) +
-                                ap_signed(x0, y0, r);
-            const size_t idx = (size_t)j * nx + i;
-            f += (double)img[idx] * frac;
-            if (rms) { double s = rms[idx]; v += s * s * frac; }
-            if (mask) fl |= mask[idx];
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        f += __shfl_xor(f, o);
-        v += __shfl_xor(v, o);
-        fl |= __shfl_xor(fl, o);
-    }
+    double f, e;
+    int32_t fl;
+    ap_wave_sum(img, rms, mask, nx, ny, xs[k], ys[k], r, lane, &f, &e, &fl);
     if (lane == 0) {
         flux[k] = f;
-        // a finite sum that rounds below 0 is 0; one that is not finite stays so (fmax alone would turn a NaN
-        // variance into an error of 0)
-        err[k] = sqrt(isfinite(v) ? fmax(v, 0.0) : v);
+        err[k] = e;
         flags[k] = fl;
     }
 }

@@ -81,6 +81,10 @@ static void vec2pix(const zm_wcs* w, const double* fr, const double v[3], double
     zm_plane2pix(w, a / c / D2R, b / c / D2R, x, y);
 }
 
+// for the units that need a pixel's unit vector or a private, order-marked copy of a WCS (lightcurve.hip)
+void zm_wcs_pix2vec(const zm_wcs* w, const double* fr, double x, double y, double v[3]) { pix2vec(w, fr, x, y, v); }
+void zm_wcs_mark_order(zm_wcs* w) { mark_order(w); }
+
 extern "C" int zm_wcs_pix2sky(const zm_wcs* w, int n, const double* x, const double* y,
                               double* ra, double* dec) {
     ZM_CHECK(w && x && y && ra && dec, "zm_wcs_pix2sky: null argument");

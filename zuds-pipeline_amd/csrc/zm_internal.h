@@ -104,6 +104,7 @@ struct zm_ctx {
     // for it and runs beside the small kernels that follow the statistics instead of beside the statistics themselves
     hipEvent_t bk_stats_event = nullptr;
     bool bk_stats_event_valid = false;
+    hipEvent_t lc_tab_event = nullptr;         // behind the last copy out of the pinned image table of lightcurve.hip
     bool timing = false;
     std::string timing_only;                   // non-empty: only this scope is timed
     std::map<std::string, zm_timer_slot> timers;
@@ -139,6 +140,8 @@ void zm_wcs_frame(const zm_wcs* w, double fr[9]);
 void zm_make_map(const zm_wcs* wout, const zm_wcs* win, zm_map_params* mp);
 void zm_map_point(const zm_map_params* mp, double xo, double yo, double* xi, double* yi);
 double zm_pixel_area(const zm_wcs* w, double x, double y);
+void zm_wcs_pix2vec(const zm_wcs* w, const double* fr, double x, double y, double v[3]);   // unit vector of a 1-based pixel
+void zm_wcs_mark_order(zm_wcs* w);             // TPV order into the flags of a PRIVATE copy (see zm_tpv_eval)
 
 // kernels / launchers (each in its own .hip)
 int zm_launch_lattice(zm_ctx* ctx, const zm_map_params* mp, int lnx, int lny, double2* lat_dev);

@@ -168,6 +168,47 @@ class CalibratedImage(CalibratableImage):
     def magzp(self):
         return self.header['MAGZP'] + self.header[APER_KEY]
 
+    @property
+    def forced_photometry(self):
+        """The ``ForcedPhotometry`` points made on this image so far (the reference's relationship, a plain list)."""
+        return self.__dict__.setdefault('_forced_photometry', [])
+
+    def force_photometry(self, sources, assume_background_subtracted=False, use_cutout=False, direct_load=None):
+        """Force aperture photometry at the locations of ``sources`` (``zuds/image.py:344-377``): one
+        ``ForcedPhotometry`` per source, in order.  Assumes that calibration has already been done.  The points are
+        returned, not recorded: the caller adds them to ``forced_photometry`` as the reference adds them to its
+        session."""
+        from .photometry import ForcedPhotometry, aperture_photometry
+        sources = np.atleast_1d(sources)
+        ra = [source.ra for source in sources]
+        dec = [source.dec for source in sources]
+        result = aperture_photometry(self, ra, dec, apply_calibration=True,
+                                     assume_background_subtracted=assume_background_subtracted,
+                                     use_cutout=use_cutout, direct_load=direct_load)
+        photometry = []
+        for k, (source, r, d) in enumerate(zip(sources, ra, dec)):
+            photometry.append(ForcedPhotometry(
+                flux=float(result['flux'][k]), fluxerr=float(result['fluxerr'][k]), flags=int(result['flags'][k]),
+                image=self, ra=r, dec=d, source=source, zp=float(result['zp'][k]),
+                obsjd=None if result['obsjd'] is None else float(result['obsjd'][k]),
+                filtercode=None if result['filtercode'] is None else str(result['filtercode'][k])))
+        return photometry
+
+    def unphotometered_sources(self, sources):
+        """The ``sources`` that lie inside this image's footprint and have no ``ForcedPhotometry`` on it yet.
+
+        The reference's property (``zuds/image.py:408-432``) asks the database: ``q3c_poly_query`` of every ``Source``
+        against the image's polygon, outer-joined to ``forcedphotometry``.  There is no database here, so the candidates
+        are handed in; the polygon test is ``footprint_join`` (``zm_footprint_join``: the same spherical quadrilateral,
+        on the GPU) and the outer join is a look at ``forced_photometry`` of this image."""
+        from .lightcurve import footprint_join
+        sources = list(np.atleast_1d(sources))
+        if not sources:
+            return []
+        _, idx = footprint_join([self.wcs], [s.ra for s in sources], [s.dec for s in sources])
+        have = {id(p.source) for p in self.forced_photometry}
+        return [sources[k] for k in idx.tolist() if id(sources[k]) not in have]
+
 
 class ScienceImage(CalibratedImage):
     """A single-epoch IPAC science frame (``zuds/image.py:435-567``)."""

@@ -7,7 +7,7 @@ from . import fits as _fits
 from .constants import APER_KEY, APERTURE_RADIUS
 from .wcs import WCS
 
-__all__ = ['PhotTable', 'raw_aperture_photometry', 'aperture_photometry']
+__all__ = ['PhotTable', 'ForcedPhotometry', 'raw_aperture_photometry', 'aperture_photometry']
 
 
 class PhotTable(dict):
@@ -17,11 +17,37 @@ class PhotTable(dict):
         self[new] = self.pop(old)
 
     def __len__(self):
-        return len(next(iter(self.values()))) if self else 0
+        return len(next(iter(self.values()))) if dict.__len__(self) else 0     # (rows, not columns)
 
     @property
     def colnames(self):
         return list(self.keys())
+
+
+class ForcedPhotometry(object):
+    """One forced-photometry point (``zuds/photometry.py:15-57``) as a plain object: the reference's columns and
+    relationships as attributes (``image``, ``source``: objects or ids), no table behind them."""
+
+    def __init__(self, flux=None, fluxerr=None, flags=None, ra=None, dec=None, zp=None, obsjd=None, filtercode=None,
+                 image=None, source=None, id=None):
+        self.flux, self.fluxerr, self.flags, self.ra, self.dec = flux, fluxerr, flags, ra, dec
+        self.zp, self.obsjd, self.filtercode, self.image, self.source, self.id = zp, obsjd, filtercode, image, source, id
+
+    @property
+    def mag(self):
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return -2.5 * np.log10(self.flux) + self.image.header['MAGZP'] + self.image.header[APER_KEY]
+
+    @property
+    def magerr(self):
+        return 1.08573620476 * self.fluxerr / self.flux
+
+    @property
+    def snr(self):
+        return self.flux / self.fluxerr
+
+    def __repr__(self):
+        return f'<ForcedPhotometry flux={self.flux!r} fluxerr={self.fluxerr!r} flags={self.flags!r} obsjd={self.obsjd!r}>'
 
 
 def _table(wcs, header, data, rms, mask, ra, dec):

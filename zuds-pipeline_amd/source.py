@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import check
-from .constants import ASSOC_RADIUS_ARCSEC, ASSOC_RB_MIN, STAR_VETO_ARCSEC
+from .constants import ASSOC_RADIUS_ARCSEC, ASSOC_RB_MIN, MJD_TO_JD, STAR_VETO_ARCSEC
 from .detections import Detection
 from .engine import get_engine
 
@@ -134,10 +134,55 @@ class Source(object):
         self.id, self.ra, self.dec = id, ra, dec
         self.detections = list(detections) if detections is not None else []
         self.score, self.altdata, self.best_detection = score, altdata, best_detection
+        self.forced_photometry = []
 
     @property
     def rejected(self):
         return bool(self.altdata) and 'rejected' in self.altdata
+
+    @property
+    def light_curve(self):
+        """The table of ``zuds/source.py:84-112`` from ``forced_photometry`` (a ``PhotTable``; a source without
+        photometry: every column present, length 0).  ``id`` is the point's own id, or its position in the list."""
+        from .photometry import PhotTable
+        pts = self.forced_photometry
+        f = lambda name: np.array([getattr(p, name) for p in pts], dtype=np.float64)
+        t = PhotTable()
+        t['mjd'] = f('obsjd') - MJD_TO_JD
+        t['filter'] = np.array(['ztf' + p.filtercode[-1] for p in pts], dtype=object)
+        t['zp'] = f('zp')
+        t['zpsys'] = np.array(['ab'] * len(pts), dtype=object)
+        t['flux'] = f('flux')
+        t['fluxerr'] = f('fluxerr')
+        t['flags'] = np.array([p.flags for p in pts], dtype=np.int64)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            t['lim_mag'] = -2.5 * np.log10(5 * t['fluxerr']) + t['zp']
+        t['id'] = np.array([k if getattr(p, 'id', None) is None else p.id for k, p in enumerate(pts)], dtype=object)
+        return t
+
+    def images(self, images, engine=None):
+        """The ``images`` (objects with a ``wcs``) whose footprint holds this source: the ``q3c_poly_query`` of
+        ``zuds/source.py:60-71`` as ``footprint_join``; the radial pre-filter of the reference is the join's own cap."""
+        from .lightcurve import footprint_join
+        images = list(images)
+        if not images:
+            return []
+        offsets, _ = footprint_join([im.wcs for im in images], [self.ra], [self.dec], engine=engine)
+        return [im for im, n in zip(images, np.diff(offsets).tolist()) if n]
+
+    def unphotometered_images(self, images=(), engine=None):
+        """Of ``images``, those that hold this source and on which it has no ``ForcedPhotometry`` yet
+        (``zuds/source.py:114-134``)."""
+        have = {id(p.image) for p in self.forced_photometry}
+        return [im for im in self.images(images, engine=engine) if id(im) not in have]
+
+    def force_photometry(self, images=(), assume_background_subtracted=True):
+        """Photometry of this source on every image of ``images`` that holds it and has none yet
+        (``zuds/source.py:136-153``); the points are returned, not recorded."""
+        out = []
+        for im in self.unphotometered_images(images):
+            out.extend(im.force_photometry(self, assume_background_subtracted=assume_background_subtracted, use_cutout=True))
+        return out
 
     def __repr__(self):
         return f'<Source {self.id} ra={self.ra:.6f} dec={self.dec:.6f} ndet={len(self.detections)} score={self.score:.3f}>'

@@ -119,6 +119,28 @@ def test_map_matches_oracle():
     np.testing.assert_allclose(yi, oyi, rtol=0, atol=1e-8)
 
 
+@pytest.mark.parametrize('name', ['crval_offset', 'across_ra_zero', 'near_pole', 'tpv_degree7_radial'])
+def test_map_matches_oracle_between_tangent_frames_and_at_degree_seven(name):
+    """zm_wcs_map where the 3 x 3 rotation between the tangent frames is not the identity (tangent points apart,
+    across RA 0, next to the pole) and where the TPV polynomial runs to degree 7 with radial terms: the scenes of
+    tests/resample_scenes.py, whose oracle positions tests/test_resample_scenes.py pins to spherical trigonometry."""
+    import resample_scenes as rs
+    z = pkg()
+    sc = rs.scene(name)
+    onx, ony = sc.wout.naxis
+    rng = np.random.default_rng(6)
+    xo = np.concatenate([[1.0, onx, 1.0, onx], rng.uniform(-20, onx + 20, 300)])
+    yo = np.concatenate([[1.0, 1.0, ony, ony], rng.uniform(-20, ony + 20, 300)])
+    xi = np.empty_like(xo)
+    yi = np.empty_like(yo)
+    a, b = z._lib.wcs_struct(sc.wout), z._lib.wcs_struct(sc.win)
+    z._lib.check(z._lib.lib().zm_wcs_map(C.byref(a), C.byref(b), xo.size, xo.ctypes.data, yo.ctypes.data,
+                                         xi.ctypes.data, yi.ctypes.data))
+    oxi, oyi = map_out_to_in(to_oracle_wcs(sc.wout), to_oracle_wcs(sc.win), xo, yo)
+    np.testing.assert_allclose(xi, oxi, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(yi, oyi, rtol=0, atol=1e-8)
+
+
 def test_flux_scale_matches_oracle():
     z = pkg()
     s = synth()

@@ -787,6 +787,52 @@ int zm_forced_photometry_batch_dev(zm_ctx* ctx, int nimg, const zm_lc_image* ima
                                    const double* dec_dev, double radius, double* x_dev, double* y_dev, double* flux_dev,
                                    double* err_dev, int32_t* flags_dev);
 
+/* ---- alert packets: cone searches against a catalogue that stays in HBM -------- */
+/* The cone searches of the reference's xmatch() (zuds/crossmatch.py: the three nearest PS1 and LegacySurvey rows within
+ * 30 arcsec, every ZTF alert, milliquas and TNS row within 1.5 arcsec) against local tables (csrc/skyindex.hip; DESIGN.md,
+ * "Alert packets").  The geometry is that of the association section, through the same arithmetic: fp64 unit vectors, two
+ * points are neighbours when their chord is <= 2 sin(r / 2) (inclusive), separations are 2 asin(min(1, chord / 2)) in arcsec.
+ * A query that is not finite matches nothing, a catalogue row that is not finite is matched by nothing.
+ *
+ * zm_skyindex_create: the index of m catalogue rows (host arrays, degrees; m = 0 .. 2^30) for queries of at most
+ * max_radius_arcsec (0.25 .. 3600): the rows sorted by cubic cell of edge chord(max_radius) (1 + 1e-6), unit vectors and
+ * row numbers of a cell contiguous.  It lives in device memory of the context's device until zm_skyindex_destroy and is
+ * never rebuilt: any number of queries, on any context of that device, read it.  The call waits; ra / dec are not kept. */
+typedef struct zm_skyindex zm_skyindex;
+int zm_skyindex_create(zm_ctx* ctx, int m, const double* ra, const double* dec, double max_radius_arcsec, zm_skyindex** out_index);
+/* the same on device arrays; the call waits as well (its work arrays are released before it returns) */
+int zm_skyindex_create_dev(zm_ctx* ctx, int m, const double* ra_dev, const double* dec_dev, double max_radius_arcsec,
+                           zm_skyindex** out_index);
+/* frees the index (NULL: nothing happens); waits for the device, so queries still in flight finish first */
+int zm_skyindex_destroy(zm_skyindex* index);
+/* out4 = rows indexed (the finite ones), cells in use, slots of the cell table, the longest probe of one insertion */
+int zm_skyindex_stats(const zm_skyindex* index, int64_t* out4);
+/* For each of n positions the k nearest catalogue rows within the radius, k = 1 .. 8:
+ *   idx[n * k]    rows of query i at i * k .., ascending by (squared chord, catalogue row); -1 in the slots not filled;
+ *   sep[n * k]    their separations in arcsec; NaN in the slots not filled;
+ *   count[n]      rows within the radius, which may exceed k.
+ * k = 1 gives the idx and sep bits of zm_crossmatch_dev.  radius_arcsec above the index's max_radius is an error
+ * (zm_last_error names both).  Device memory, enqueued on the context's stream, nothing waited for.  n = 0: nothing
+ * happens; an index of no rows: every idx is -1 and every count 0.  The result does not depend on the order of the rows
+ * inside a cell: it is the same bytes on every run. */
+int zm_cone_knn_dev(zm_ctx* ctx, const zm_skyindex* index, int n, const double* ra_dev, const double* dec_dev,
+                    double radius_arcsec, int k, int32_t* idx_dev, double* sep_dev, int32_t* count_dev);
+/* the same on host arrays: copied in, the call waits */
+int zm_cone_knn(zm_ctx* ctx, const zm_skyindex* index, int n, const double* ra, const double* dec, double radius_arcsec, int k,
+                int32_t* idx, double* sep, int32_t* count);
+/* Every catalogue row within the radius of each of n positions, as zm_footprint_join_dev returns its pairs:
+ *   offsets[n + 1]      int64, device: the rows of query i are entries offsets[i] .. offsets[i + 1] - 1 of cat_idx;
+ *                       always complete, offsets[n] is the number of pairs whatever the capacity;
+ *   cat_idx[capacity]   int32, device: catalogue rows, ascending within a query; the same bytes on every run;
+ *   *out_npairs         host: the number of pairs.  When it exceeds `capacity`, only the first `capacity` entries of cat_idx
+ *                       were written and nothing past them: call again with room for all.
+ * The call waits for that one word (offsets are complete then; cat_idx is enqueued behind it). */
+int zm_cone_within_dev(zm_ctx* ctx, const zm_skyindex* index, int n, const double* ra_dev, const double* dec_dev,
+                       double radius_arcsec, int64_t capacity, int64_t* offsets_dev, int32_t* cat_idx_dev, int64_t* out_npairs);
+/* the same on host arrays: copied in, the call waits; min(*out_npairs, capacity) entries of cat_idx are written */
+int zm_cone_within(zm_ctx* ctx, const zm_skyindex* index, int n, const double* ra, const double* dec, double radius_arcsec,
+                   int64_t capacity, int64_t* offsets, int32_t* cat_idx, int64_t* out_npairs);
+
 /* ---- astrometric refit: detections against a star catalogue -> the PV terms of a TPV header ---- */
 /* Stands where the reference runs SCAMP (zuds/scamp.py:16-113, astromatic/default.scamp); the operator is stated in
  * DESIGN.md, "Astrometric refit" (csrc/astrometry.hip): a vote for the gross offset (MATCH Y, POSITION_MAXERR), then rounds

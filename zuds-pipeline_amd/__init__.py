@@ -29,8 +29,12 @@ from .catalog import *
 from .detections import *
 from .thumbnails import *
 from .realbogus import *
+# (before .source: the package attribute `crossmatch` stays source.crossmatch, the function, as it was; the module
+# is reached as importlib.import_module('zuds-pipeline_amd.crossmatch'))
+from .crossmatch import SkyIndex, ExternalCatalog, xmatch
 from .source import *
 from .lightcurve import *
+from .alert import *
 from .scamp import *
 from . import synth, fits, scamp, lightcurve
 

@@ -302,6 +302,14 @@ _SIGS = {
                                     C.POINTER(C.c_int64)]),
     'zm_forced_photometry_batch_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_lc_image), _P, _P, C.c_int64, C.c_int, _P, _P,
                                                  C.c_double, _P, _P, _P, _P, _P]),
+    'zm_skyindex_create': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, C.POINTER(_P)]),
+    'zm_skyindex_create_dev': (C.c_int, [_P, C.c_int, _P, _P, C.c_double, C.POINTER(_P)]),
+    'zm_skyindex_destroy': (C.c_int, [_P]),
+    'zm_skyindex_stats': (C.c_int, [_P, _P]),
+    'zm_cone_knn_dev': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_double, C.c_int, _P, _P, _P]),
+    'zm_cone_knn': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_double, C.c_int, _P, _P, _P]),
+    'zm_cone_within_dev': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_double, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
+    'zm_cone_within': (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_double, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
     'zm_astrom_params_default': (None, [C.POINTER(zm_astrom_params)]),
     'zm_astrom_solve_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_wcs), _P, _P, _P, _P, _P, C.c_int, _P, _P, _P,
                                       C.POINTER(zm_astrom_params), C.POINTER(zm_astrom_result), _P, _P]),

@@ -530,7 +530,7 @@ typedef struct zm_object {
     int32_t number;          /* NUMBER */
     int32_t npix;            /* ISOAREA_IMAGE */
     int32_t xmin, xmax, ymin, ymax;   /* XMIN_IMAGE .. YMAX_IMAGE */
-    int32_t flags;           /* FLAGS: 4 saturated, 8 on the frame border, 16 aperture incomplete */
+    int32_t flags;           /* FLAGS: 2 deblended (zm_extract_deblend only), 4 saturated, 8 on the frame border, 16 aperture incomplete */
     int32_t flags_weight;    /* FLAGS_WEIGHT: 1 = a bad pixel touches the object */
     int32_t imaflags_iso;    /* IMAFLAGS_ISO: OR of the flag plane over the object */
     int32_t first;           /* 0-based linear index of the object's first pixel in raster order */
@@ -562,6 +562,36 @@ int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
                const zm_extract_params* params, int max_objects, zm_object* out_rows,
                int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
                int* out_status);
+
+/* ---- source extraction with multi-threshold deblending (opt-in) -------------- */
+/* DEBLEND_NTHRESH / DEBLEND_MINCONT of sextractor.conf.  zm_extract and its results are what they were; these entry
+ * points run the same first pass and then split every object whose tree of nthresh exponentially spaced levels has at
+ * least two significant branches ("Deblending"; restated in tests/deblend_ref.py).  Objects, split or not, are
+ * renumbered 1 .. n in raster order of their first pixel and measured on their own pixels; the sub-objects of a split
+ * parent carry FLAGS bit 2.  Where nothing splits, rows and map equal those of zm_extract bit for bit.  There is no
+ * CLEAN pass: the mincont test is the only guard against shredding. */
+typedef struct zm_deblend_params {
+    int32_t nthresh;         /* DEBLEND_NTHRESH (32): a power of two in 2 .. 64 */
+    int32_t pad_;
+    double mincont;          /* DEBLEND_MINCONT (0.005): in [0, 1] */
+} zm_deblend_params;
+void zm_deblend_params_default(zm_deblend_params* p);
+
+#define ZM_EXTRACT_DEBLEND 2     /* status bit: a loop of the deblending kernel reached its bound (results are not to be used) */
+
+/* The arguments of zm_extract_dev, then the deblending parameters and out_parent (host array of max_objects int32, or
+ * NULL): the first-pass NUMBER of the object each row was part of. */
+int zm_extract_deblend_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                           const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                           const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                           int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
+                           int* out_status, const zm_deblend_params* deblend, int32_t* out_parent);
+/* The same with host planes. */
+int zm_extract_deblend(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                       const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                       const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                       int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
+                       int* out_status, const zm_deblend_params* deblend, int32_t* out_parent);
 
 /* ---- source extraction, second pass: the Kron and windowed columns of sextractor.param ---- */
 /* Opt-in: zm_extract and its table are what they were.  Measures, for rows zm_extract wrote, the columns of

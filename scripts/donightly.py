@@ -6,7 +6,7 @@ subtractions as one batch of launches on each of J lanes (``nightly.SubtractionP
 ``--fit-batch 0``: J separate subtractions in flight).
 
 usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch B] [--batch FRAMES] [--nreg-side N]
-                    [--detect [--stamps] [--rb-model BASE [--rb-cut X]] [--associate [--stars F]]]
+                    [--detect [--stamps] [--deblend] [--rb-model BASE [--rb-cut X]] [--associate [--stars F]]]
 
 * ``images.txt``: science image paths (``*sciimg.fits``; the mask is ``*mskimg.fits``; a
   ``.weight.fits`` sibling is required: 1 / rms^2, 0 on bad pixels).  The list is sharded over
@@ -24,7 +24,9 @@ Products per image, with the reference's names: ``sub.<sci>_<ref>.fits``, ``.rms
 ``dosub.py --detect``: what ``dosub.do_one`` hands back to the reference's night), made on the planes in HBM
 (``DeviceSubtraction.candidates``).  ``--stamps`` (needs ``--detect``): and ``sub.*.stamps.fits``, the thumbnails of
 its ``GOODCUT == 1`` rows in the layout of ``dosub.py --stamps``; more than 50 such rows: no stamps file (the
-reference's TooManyDetectionsError).  ``--associate`` (needs ``--detect``): once the pool has drained, the night's
+reference's TooManyDetectionsError).  ``--deblend`` (needs ``--detect``): the extraction deblends (``DEBLEND_NTHRESH`` 32,
+``DEBLEND_MINCONT`` 0.005; DESIGN.md "Deblending"): the tables carry ``PARENT_NUMBER`` and the headers say ``ZMDEBLND = T``.
+``--associate`` (needs ``--detect``): once the pool has drained, the night's
 in-memory tables go through ``zuds.associate`` (the job of ``nersc/makesources.py``; ``scripts/makesources.py`` does the
 same from the ``sub.*.cat`` files) and ``<images>.sources.txt`` / ``<images>.sources.det.txt`` are written next to the
 image list; ``--stars F``: ``ra dec`` per line, the star veto."""
@@ -120,6 +122,7 @@ def write_detections(out, hdr, ref, res):
     cat.basename = name.replace('.fits', '.cat')
     cat.map_to_local_file(out.replace('.fits', '.cat'))
     cat.data, cat.header, cat.header_comments = res['cat'], dict(hdr), {}
+    cat.deblend = res.get('deblend')
     cat.save()
     if res.get('too_many'):
         print(f'Error: {int((res["cat"]["GOODCUT"] == 1).sum())} detections (>{MAX_DETS}) '
@@ -185,6 +188,8 @@ def main(argv=None):
                          'groups, two lanes of 16 1.95 / 2.8, 8 - 16 separate chains 3.0); 0: one chain per job')
     ap.add_argument('--detect', action='store_true', help='write the filtered detection catalog sub.*.cat of every subtraction')
     ap.add_argument('--stamps', action='store_true', help='with --detect: write sub.*.stamps.fits, the thumbnails of the detections')
+    ap.add_argument('--deblend', action='store_true', help='with --detect: multi-threshold deblending (DEBLEND_NTHRESH 32, '
+                                                           'DEBLEND_MINCONT 0.005); the catalogs say ZMDEBLND = T')
     ap.add_argument('--rb-model', help='with --detect: BASE of BASE.architecture.json + BASE.weights.npz, the real / bogus '
                                        'network the candidate filter ends with (realbogus.load_model)')
     ap.add_argument('--rb-cut', type=float, help='with --rb-model: the score below which a candidate is cut; default '
@@ -198,6 +203,9 @@ def main(argv=None):
         return 2
     if args.stamps and not args.detect:
         print('--stamps needs --detect', file=sys.stderr)
+        return 2
+    if args.deblend and not args.detect:
+        print('--deblend needs --detect', file=sys.stderr)
         return 2
     if (args.rb_model or args.rb_cut is not None) and not args.detect:
         print('--rb-model needs --detect', file=sys.stderr)
@@ -226,7 +234,8 @@ def main(argv=None):
     tables = [] if args.associate else None
     try:
         done = run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side,
-                         detect=args.detect, stamps=args.stamps, rb_model=rb_model, rb_cut=args.rb_cut, tables=tables)
+                         detect=args.detect, stamps=args.stamps, rb_model=rb_model, rb_cut=args.rb_cut, tables=tables,
+                         deblend=args.deblend)
     finally:
         pool.close()
         ring.close()
@@ -252,7 +261,7 @@ def make_sources(tables, prefix, stars=None, engine=None):
 
 
 def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False, rb_model=None,
-              rb_cut=None, tables=None):
+              rb_cut=None, tables=None, deblend=False):
     """The images of this rank against one reference.  The files of batch b + 1 are read, sent and decoded by the
     ring (fitsring.FITSRing: reader threads, copy stream) while the pool subtracts batch b; the products of batch b
     are encoded on the device, copied back on a third stream and written by the ring's writer threads while
@@ -313,7 +322,7 @@ def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, dete
                     # the filter id as image.py reads it; a frame without the card and no --rb-cut fails here (ValueError)
                     rbkw = dict(rb_model=rb_model, rb_cut=rb_cut, fid=hdr.get('FID', hdr.get('FILTERID')))
                 job = nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
-                                             stamps=stamps, max_detections=MAX_DETS, **rbkw)
+                                             stamps=stamps, max_detections=MAX_DETS, deblend=deblend, **rbkw)
             except Exception:
                 # (the reference's drivers: try / except per image, scripts/dosub.py:205-213)
                 traceback.print_exception(*sys.exc_info())

@@ -2,7 +2,7 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns] [--rb-model BASE [--rb-cut X]]]
+usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns] [--deblend] [--rb-model BASE [--rb-cut X]]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
@@ -12,6 +12,8 @@ With ``--param-columns`` (needs ``--detect``) the catalog holds every column of 
 ``XWIN_WORLD``, ... : ``extract.PARAM_COLUMNS``) and the ds9 region file ``sub.*.reg`` is written next to it
 once the detections have been filtered (``PipelineRegionFile.from_catalog``: green where ``GOODCUT`` is set, red
 elsewhere).
+With ``--deblend`` (needs ``--detect``) the extraction deblends (``DEBLEND_NTHRESH`` 32, ``DEBLEND_MINCONT`` 0.005): the
+catalog's header says ``ZMDEBLND = T`` and its table carries ``PARENT_NUMBER``.
 With ``--stamps`` (needs ``--detect``) every detection also gets its three thumbnails - difference, new and reference
 image on the reference image's grid (``Thumbnail.from_detections``, dosub.py:133-150) - and ``sub.*.stamps.fits`` is
 written next to the catalog: the zero-filled blocks ``[n, 3, 63, 63]`` (sub, new, ref) and a table with ``ra``, ``dec``,
@@ -74,7 +76,7 @@ def write_stamps(sub, detections, stamps, size=None):
 
 
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
-           rb_cut=None):
+           rb_cut=None, deblend=False):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -116,7 +118,8 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
     detections = None
     if detect:
         catstart = time.time()
-        cat = zuds.PipelineFITSCatalog.from_image(sub, columns='param' if param_columns else 'isophotal')
+        cat = zuds.PipelineFITSCatalog.from_image(sub, columns='param' if param_columns else 'isophotal',
+                                                   deblend=deblend)
         catstop = time.time()
         print(f'cat: {catstop - catstart:.2f} sec to make catalog for {sub.basename}', flush=True)
         dstart = time.time()
@@ -162,6 +165,10 @@ def main(argv):
     if param_columns and not detect:
         print('--param-columns needs --detect', file=sys.stderr)
         return 2
+    deblend = '--deblend' in argv
+    if deblend and not detect:
+        print('--deblend needs --detect', file=sys.stderr)
+        return 2
     argv = list(argv)
     rb_model = rb_cut = None
     for flag in ('--rb-model', '--rb-cut'):
@@ -184,7 +191,7 @@ def main(argv):
         return 2
     if rb_model:
         rb_model = zuds.load_model(rb_model)
-    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns')]
+    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend')]
     infile = args[0]
     refname = args[1]
     subclass = zuds.SingleEpochSubtraction
@@ -193,7 +200,7 @@ def main(argv):
     for fn in imgs:
         try:
             do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
-                   rb_model=rb_model, rb_cut=rb_cut)
+                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

@@ -12,6 +12,10 @@ events, per call:
   host included);
 * ``extract_param_ms``  the same call with ``columns='param'``: the second pass (``k_ex_kron``, ``k_ex_win``) and its
   table on top; ``param_over_default`` is its ratio to ``extract_ms`` of the same run;
+* ``extract_deblend_ms``  the same call with ``deblend=True`` (``k_db_tree`` and a second numbering on top);
+  ``deblend_over_default`` is its ratio to ``extract_ms`` of the same run, ``objects_deblend`` what it finds;
+* ``crowded_ms`` / ``crowded_deblend_ms``  both calls on a crowded field of ``--crowded-size`` px a side: 3000 stars under
+  noise 1, a third of them companions 3 .. 6 px from another star (``crowded_objects`` / ``crowded_objects_deblend``);
 * ``copy_ms``      a float4 copy (``zm_copy_probe_dev``) that moves the bytes of the planes the extractor has to touch
   at least once: image, noise, flag plane, segmentation map (4 B per pixel each) and the bad-pixel map (1 B).  The copy
   cycles through four source / destination pairs (640 MB in all at the default size), more than the 256 MB last-level
@@ -42,6 +46,7 @@ def main():
     ap.add_argument('--frames', type=int, default=8)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--crowded-size', type=int, default=1024)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -94,6 +99,28 @@ def main():
         tab, nfound, _ = sub.extract(columns='param')
         found['wide'] = len(tab.dtype.names)
 
+    def extract_deblend():
+        tab, nfound, _ = sub.extract(deblend=True)
+        found['deblend'] = nfound
+
+    # the crowded field: 2000 stars and 1000 companions 3 .. 6 px from one of them, noise 1
+    csize = args.crowded_size
+    rng = np.random.default_rng(31)
+    cx, cy = rng.uniform(5, csize - 5, 2000), rng.uniform(5, csize - 5, 2000)
+    sep, ang = rng.uniform(3.0, 6.0, 1000), rng.uniform(0.0, 2.0 * np.pi, 1000)
+    cx = np.concatenate([cx, cx[:1000] + sep * np.cos(ang)])
+    cy = np.concatenate([cy, cy[:1000] + sep * np.sin(ang)])
+    field = rng.normal(0.0, 1.0, (csize, csize))
+    synth.add_stars(field, cx, cy, 10 ** rng.uniform(2.3, 4.0, 3000), 2.4)
+    cimg = torch.from_numpy(field.astype(np.float32)).to(device)
+    cone = torch.ones((csize, csize), dtype=torch.float32, device=device)
+
+    def crowded():
+        tab, found['crowded'] = eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize)
+
+    def crowded_deblend():
+        tab, found['crowded_deblend'] = eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize, deblend=True)
+
     nbytes = (17 * size * size // 2) // 16 * 16
     pairs = [(torch.zeros(nbytes, dtype=torch.uint8, device=device), torch.empty(nbytes, dtype=torch.uint8, device=device))
              for _ in range(4)]
@@ -121,6 +148,9 @@ def main():
     s_med, s_min = clock(subtract)
     e_med, e_min = clock(extract)
     p_med, p_min = clock(extract_param)
+    d_med, d_min = clock(extract_deblend)
+    cr_med, _ = clock(crowded)
+    crd_med, _ = clock(crowded_deblend)
     c_med, c_min = clock(copy)
     flat = torch.full((size, size), 100.0, dtype=torch.float32, device=device)
     one = torch.ones((size, size), dtype=torch.float32, device=device)
@@ -137,6 +167,10 @@ def main():
                extract_ms=round(e_med, 4), extract_ms_min=round(e_min, 4),
                extract_param_ms=round(p_med, 4), extract_param_ms_min=round(p_min, 4), param_columns=found.get('wide'),
                param_over_default=round(p_med / e_med, 2),
+               extract_deblend_ms=round(d_med, 4), extract_deblend_ms_min=round(d_min, 4), objects_deblend=found.get('deblend'),
+               deblend_over_default=round(d_med / e_med, 2), crowded_size=csize, crowded_ms=round(cr_med, 4),
+               crowded_deblend_ms=round(crd_med, 4), crowded_objects=found.get('crowded'),
+               crowded_objects_deblend=found.get('crowded_deblend'),
                copy_ms=round(c_med, 4), copy_bytes_per_pixel=17,
                extract_over_subtract=round(e_med / s_med, 3), extract_over_copy=round(e_med / c_med, 2))
     line = json.dumps(out)

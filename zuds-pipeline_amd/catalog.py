@@ -16,11 +16,21 @@ from .file import File, UnmappedFileError
 
 __all__ = ['PipelineFITSCatalog', 'PipelineRegionFile']
 
-# what this version of the extractor does not do, stated in every catalog's header
+# what the extraction behind a catalog did not do, stated in its header (a catalog made with deblend=: header_cards)
 HEADER_CARDS = [('ZMDEBLND', False, 'multi-threshold deblending (not in this version)'),
                 ('ZMCLEAN', False, 'CLEAN pass (not in this version)')]
+
 # ... and of a wide table: the Kron and windowed sums do not mask the pixels of other objects
 WIDE_CARDS = [('ZMMASKTY', 'NONE', 'MASK_TYPE of the Kron and windowed sums')]
+
+
+def header_cards(deblend=None):
+    """The cards every catalog's header states the extractor's steps with; ``deblend``: None, or the
+    dict(nthresh=, mincont=) the catalog was made with."""
+    if not deblend:
+        return list(HEADER_CARDS)
+    return [('ZMDEBLND', True, 'multi-threshold deblending'), ('ZMDBNTHR', int(deblend['nthresh']), 'DEBLEND_NTHRESH'),
+            ('ZMDBMINC', float(deblend['mincont']), 'DEBLEND_MINCONT')] + HEADER_CARDS[1:]
 
 
 # the two lines every region file starts with (ds9: global properties, then the coordinate system)
@@ -63,13 +73,14 @@ class PipelineFITSCatalog(File):
     header = None                 # header of the image the catalog was made from (LDAC_IMHEAD)
     header_comments = None
     image = None
+    deblend = None                # dict(nthresh=, mincont=) of a catalog made with deblending
 
     @classmethod
-    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal'):
+    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal', deblend=False):
         from .image import CalibratableImageBase
         if not isinstance(image, CalibratableImageBase):
             raise ValueError('Image is not an instance of CalibratableImage.')
-        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns)
+        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns, deblend=deblend)
         cat = image.catalog
         for prop in GROUP_PROPERTIES:
             setattr(cat, prop, getattr(image, prop, None))
@@ -102,6 +113,8 @@ class PipelineFITSCatalog(File):
 
     def load(self):
         self._data, self.table_header, self.header, self.header_comments = _fits.read_ldac(self.local_path)
+        if self.table_header.get('ZMDEBLND') is True:
+            self.deblend = dict(nthresh=int(self.table_header['ZMDBNTHR']), mincont=float(self.table_header['ZMDBMINC']))
 
     def save(self):
         try:
@@ -111,7 +124,7 @@ class PipelineFITSCatalog(File):
             self.map_to_local_file(f)
         wide = 'FLUX_AUTO' in (self.data.dtype.names or ())
         _fits.write_ldac(f, self.data, self.header or {}, self.header_comments or {},
-                         extra=HEADER_CARDS + (WIDE_CARDS if wide else []))
+                         extra=header_cards(self.deblend) + (WIDE_CARDS if wide else []))
 
     def kill_flagged(self):
         """Drop the detections with a bad IMAFLAGS_ISO or a bad pixel next to them (``zuds/catalog.py:132-142``); a

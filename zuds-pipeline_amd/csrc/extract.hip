@@ -26,7 +26,6 @@
 #define EX_TH 8
 #define EX_SCAN_ROUNDS 8
 #define EX_SCAN_SPAN (256 * EX_SCAN_ROUNDS)
-#define EX_OI 8                      // ints per object: xmin, xmax, ymin, ymax, npix, flag OR, bits, root
 #define EX_BIT_SAT 4
 #define EX_BIT_BADNBR 256
 
@@ -548,11 +547,9 @@ static void ex_finish_row(zm_object* r, const int* o, const ex_meas& m, int numb
     r->x_world = r->y_world = NAN;
 }
 
-extern "C" int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
-                              const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
-                              const zm_extract_params* params, int max_objects, zm_object* out_rows,
-                              int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
-                              int* out_status) {
+// The stages of zm_extract_dev, shared with the deblending entry point (deblend.hip; declared in zm_internal.h).
+int zm_ex_check(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_extract_params* params,
+                int max_objects, const zm_object* out_rows, const int* out_nwritten, const int* out_nfound) {
     ZM_CHECK(ctx && img && sigma && params && out_nwritten && out_nfound, "zm_extract: null argument");
     // rows go on gridDim.y, four per workgroup of the filter: 65535 x 4 rows at the most
     ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30 && ny <= 65535 * 4,
@@ -563,49 +560,74 @@ extern "C" int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma,
                  params->aper_radius > 0 && params->aper_radius < 512,
              "zm_extract: bad parameters (thresh %g, minarea %d, filter %d, radius %g)", (double)params->detect_thresh,
              params->detect_minarea, params->filter, params->aper_radius);
-    ZM_HIP(hipSetDevice(ctx->device));
+    return 0;
+}
+
+// scratch planes; the status word and the counters are cleared
+int zm_ex_planes(zm_ctx* ctx, int nx, int ny, int32_t* segm_dev, float* filtered_dev, zm_ex_bufs* b) {
     const int np = nx * ny;
-    const int cap = max_objects;
-    const int nsb = zm_div_up(np, EX_SCAN_SPAN);
-    float* d_filt = filtered_dev;
-    int *d_seg = segm_dev, *d_label = nullptr, *d_cnt = nullptr, *d_bad32 = nullptr, *d_small = nullptr, *d_obj = nullptr;
-    if (!d_filt) ZM_TRY(ctx->get("ex_filt", (size_t)np * 4, (void**)&d_filt));
-    if (!d_seg) ZM_TRY(ctx->get("ex_seg", (size_t)np * 4, (void**)&d_seg));
-    ZM_TRY(ctx->get("ex_label", (size_t)np * 4, (void**)&d_label));
-    ZM_TRY(ctx->get("ex_cnt", (size_t)np * 4, (void**)&d_cnt));
-    ZM_TRY(ctx->get("ex_bad32", (size_t)np * 4, (void**)&d_bad32));
-    ZM_TRY(ctx->get("ex_small", (size_t)(nsb + 4) * 4, (void**)&d_small));
-    ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
-    int *d_status = d_small, *d_nobj = d_small + 1, *d_blocks = d_small + 4;
-    ZM_HIP(hipMemsetAsync(d_small, 0, 16, ctx->stream));
-    const bool vec = nx % 4 == 0 && (((uintptr_t)img | (uintptr_t)sigma | (uintptr_t)d_filt | (uintptr_t)d_label |
-                                      (uintptr_t)d_cnt | (uintptr_t)d_bad32) & 15) == 0 && ((uintptr_t)bad & 3) == 0;
+    b->np = np;
+    b->nsb = zm_div_up(np, EX_SCAN_SPAN);
+    b->filt = filtered_dev;
+    b->seg = segm_dev;
+    if (!b->filt) ZM_TRY(ctx->get("ex_filt", (size_t)np * 4, (void**)&b->filt));
+    if (!b->seg) ZM_TRY(ctx->get("ex_seg", (size_t)np * 4, (void**)&b->seg));
+    ZM_TRY(ctx->get("ex_label", (size_t)np * 4, (void**)&b->label));
+    ZM_TRY(ctx->get("ex_cnt", (size_t)np * 4, (void**)&b->cnt));
+    ZM_TRY(ctx->get("ex_bad32", (size_t)np * 4, (void**)&b->bad32));
+    ZM_TRY(ctx->get("ex_small", (size_t)(b->nsb + 4) * 4, (void**)&b->small));
+    ZM_HIP(hipMemsetAsync(b->small, 0, 16, ctx->stream));
+    return 0;
+}
+
+// filter, threshold, labelling, pixels per root
+void zm_ex_label(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, int nx, int ny,
+                 const zm_extract_params* params, const zm_ex_bufs* b) {
+    const int np = b->np;
+    int* d_status = b->small;
+    const bool vec = nx % 4 == 0 && (((uintptr_t)img | (uintptr_t)sigma | (uintptr_t)b->filt | (uintptr_t)b->label |
+                                      (uintptr_t)b->cnt | (uintptr_t)b->bad32) & 15) == 0 && ((uintptr_t)bad & 3) == 0;
     const dim3 tiles(zm_div_up(nx, EX_TW), zm_div_up(ny, EX_TH)), tile(EX_TW, EX_TH);
     const int nlin = zm_div_up(np, 256);
     hipLaunchKernelGGL(k_ex_filter, dim3(zm_div_up(zm_div_up(nx, 4), 64), zm_div_up(ny, 4)), dim3(64, 4), 0, ctx->stream, img,
-                       sigma, bad, nx, ny, params->detect_thresh, params->filter, vec ? 1 : 0, d_filt, d_label, d_cnt, d_bad32);
-    hipLaunchKernelGGL(k_ex_local, tiles, tile, 0, ctx->stream, d_label, nx, ny, d_status);
-    hipLaunchKernelGGL(k_ex_border, tiles, tile, 0, ctx->stream, d_label, nx, ny, np, d_status);
-    hipLaunchKernelGGL(k_ex_flatten, dim3(nlin), dim3(256), 0, ctx->stream, d_label, np, np, d_status);
-    hipLaunchKernelGGL(k_ex_count, dim3(nlin), dim3(256), 0, ctx->stream, d_label, np, d_cnt);
-    hipLaunchKernelGGL(k_ex_scan1, dim3(nsb), dim3(256), 0, ctx->stream, d_label, d_cnt, np, params->detect_minarea, d_blocks);
-    hipLaunchKernelGGL(k_ex_scan2, dim3(1), dim3(1024), 0, ctx->stream, d_blocks, nsb, d_nobj);
-    if (cap > 0) hipLaunchKernelGGL(k_ex_objinit, dim3(zm_div_up(cap, 256)), dim3(256), 0, ctx->stream, d_obj, cap);
-    hipLaunchKernelGGL(k_ex_scan3, dim3(nsb), dim3(256), 0, ctx->stream, d_label, d_cnt, np, params->detect_minarea, d_blocks,
-                       cap, d_obj);
-    hipLaunchKernelGGL(k_ex_relabel, dim3(nlin), dim3(256), 0, ctx->stream, d_label, d_cnt, img, flag, d_bad32, nx, ny,
-                       params->satur_level, cap, d_seg, d_obj);
-    ZM_HIP(hipGetLastError());
-    int head[2] = {0, 0};
-    ZM_HIP(hipMemcpyAsync(head, d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_status) *out_status = head[0];
-    *out_nfound = head[1];
-    const int n = head[1] < cap ? head[1] : cap;
-    *out_nwritten = n;
-    ZM_CHECK(head[0] == 0, "zm_extract: a label chain passed its bound of %d steps (status %d)", np, head[0]);
-    if (n == 0) return 0;
+                       sigma, bad, nx, ny, params->detect_thresh, params->filter, vec ? 1 : 0, b->filt, b->label, b->cnt,
+                       b->bad32);
+    hipLaunchKernelGGL(k_ex_local, tiles, tile, 0, ctx->stream, b->label, nx, ny, d_status);
+    hipLaunchKernelGGL(k_ex_border, tiles, tile, 0, ctx->stream, b->label, nx, ny, np, d_status);
+    hipLaunchKernelGGL(k_ex_flatten, dim3(nlin), dim3(256), 0, ctx->stream, b->label, np, np, d_status);
+    hipLaunchKernelGGL(k_ex_count, dim3(nlin), dim3(256), 0, ctx->stream, b->label, np, b->cnt);
+}
 
+// pixels per root of another label plane, into the cleared counter plane
+int zm_ex_recount(zm_ctx* ctx, const int* label, const zm_ex_bufs* b) {
+    ZM_HIP(hipMemsetAsync(b->cnt, 0, (size_t)b->np * 4, ctx->stream));
+    hipLaunchKernelGGL(k_ex_count, dim3(zm_div_up(b->np, 256)), dim3(256), 0, ctx->stream, label, b->np, b->cnt);
+    return 0;
+}
+
+// `label` holds, for every foreground pixel, the smallest linear index of its object, and b->cnt the pixels per root
+void zm_ex_count_roots(zm_ctx* ctx, const int* label, int minarea, const zm_ex_bufs* b) {
+    hipLaunchKernelGGL(k_ex_scan1, dim3(b->nsb), dim3(256), 0, ctx->stream, label, b->cnt, b->np, minarea, b->small + 4);
+    hipLaunchKernelGGL(k_ex_scan2, dim3(1), dim3(1024), 0, ctx->stream, b->small + 4, b->nsb, b->small + 1);
+}
+
+// numbering, segmentation map into `seg`, integer reductions into `obj` (cap rows)
+void zm_ex_number(zm_ctx* ctx, const int* label, const float* img, const int32_t* flag, int nx, int ny,
+                  const zm_extract_params* params, int cap, int* seg, int* obj, const zm_ex_bufs* b) {
+    const int nlin = zm_div_up(b->np, 256);
+    if (cap > 0) hipLaunchKernelGGL(k_ex_objinit, dim3(zm_div_up(cap, 256)), dim3(256), 0, ctx->stream, obj, cap);
+    hipLaunchKernelGGL(k_ex_scan3, dim3(b->nsb), dim3(256), 0, ctx->stream, label, b->cnt, b->np, params->detect_minarea,
+                       b->small + 4, cap, obj);
+    hipLaunchKernelGGL(k_ex_relabel, dim3(nlin), dim3(256), 0, ctx->stream, label, b->cnt, img, flag, b->bad32, nx, ny,
+                       params->satur_level, cap, seg, obj);
+}
+
+// rows 0 .. n - 1 from the segmentation map and the object table
+int zm_ex_rows(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_wcs* wcs,
+               const zm_extract_params* params, int n, const int* d_seg, const int* d_obj, const zm_ex_bufs* b,
+               zm_object* out_rows) {
+    const float* d_filt = b->filt;
+    const int* d_bad32 = b->bad32;
     char* d_m = nullptr;
     const size_t apbytes = (size_t)n * (4 * sizeof(double) + 2 * sizeof(int32_t));
     ZM_TRY(ctx->get("ex_meas", (size_t)n * sizeof(ex_meas) + apbytes + 64, (void**)&d_m));
@@ -651,11 +673,40 @@ extern "C" int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma,
     return 0;
 }
 
-extern "C" int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
-                          const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
-                          const zm_extract_params* params, int max_objects, zm_object* out_rows,
-                          int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
-                          int* out_status) {
+extern "C" int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                              const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                              const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                              int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
+                              int* out_status) {
+    ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
+    ZM_HIP(hipSetDevice(ctx->device));
+    const int np = nx * ny;
+    const int cap = max_objects;
+    zm_ex_bufs b;
+    int* d_obj = nullptr;
+    ZM_TRY(zm_ex_planes(ctx, nx, ny, segm_dev, filtered_dev, &b));
+    ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
+    zm_ex_label(ctx, img, sigma, bad, nx, ny, params, &b);
+    zm_ex_count_roots(ctx, b.label, params->detect_minarea, &b);
+    zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
+    ZM_HIP(hipGetLastError());
+    int head[2] = {0, 0};
+    ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    ZM_HIP(hipStreamSynchronize(ctx->stream));
+    if (out_status) *out_status = head[0];
+    *out_nfound = head[1];
+    const int n = head[1] < cap ? head[1] : cap;
+    *out_nwritten = n;
+    ZM_CHECK(head[0] == 0, "zm_extract: a label chain passed its bound of %d steps (status %d)", np, head[0]);
+    if (n == 0) return 0;
+    return zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows);
+}
+
+// host planes in, host planes out, for zm_extract (deblend == nullptr) and zm_extract_deblend
+int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* flag, int nx, int ny,
+               const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows, int32_t* out_segm,
+               float* out_filtered, int* out_nwritten, int* out_nfound, int* out_status, const zm_deblend_params* deblend,
+               int32_t* out_parent) {
     ZM_CHECK(ctx && img && sigma, "zm_extract: null argument");
     // rows go on gridDim.y, four per workgroup of the filter: 65535 x 4 rows at the most
     ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30 && ny <= 65535 * 4,
@@ -680,12 +731,23 @@ extern "C" int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, con
     ZM_TRY(ctx->get("ex_seg", np * 4, (void**)&d_seg));
     ZM_TRY(ctx->get("ex_filt", np * 4, (void**)&d_filt));
     int st = 0;
-    const int rc = zm_extract_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows, d_seg, d_filt,
-                                  out_nwritten, out_nfound, &st);
+    const int rc = deblend ? zm_extract_deblend_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows,
+                                                    d_seg, d_filt, out_nwritten, out_nfound, &st, deblend, out_parent)
+                           : zm_extract_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows, d_seg,
+                                            d_filt, out_nwritten, out_nfound, &st);
     if (out_status) *out_status = st;
     if (rc != 0 && st == 0) return rc;                   // with the status word set the planes still come back: they show where
     if (out_segm) ZM_HIP(hipMemcpyAsync(out_segm, d_seg, np * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (out_filtered) ZM_HIP(hipMemcpyAsync(out_filtered, d_filt, np * 4, hipMemcpyDeviceToHost, ctx->stream));
     ZM_HIP(hipStreamSynchronize(ctx->stream));
     return rc;
+}
+
+extern "C" int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                          const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                          const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                          int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
+                          int* out_status) {
+    return zm_ex_host(ctx, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, out_rows, out_segm, out_filtered,
+                      out_nwritten, out_nfound, out_status, nullptr, nullptr);
 }

@@ -241,3 +241,28 @@ int zm_launch_mask_accum(zm_ctx* ctx, int32_t* acc, const int32_t* m, int64_t np
 int zm_launch_mask_finalize(zm_ctx* ctx, int32_t* acc, float* cov, int64_t npix);
 int zm_launch_split_pairs(zm_ctx* ctx, const float2* src, int64_t npix, float* a, float* b);
 int zm_launch_mask_widen(zm_ctx* ctx, const int16_t* in, int64_t n, int32_t* out);
+
+// ---- source extraction: the stages of zm_extract_dev (extract.hip), which zm_extract_deblend_dev (deblend.hip) reuses ----
+#define EX_OI 8                      // ints per object: xmin, xmax, ymin, ymax, npix, flag OR, bits, root
+struct zm_ex_bufs {
+    float* filt;                     // filtered plane
+    int *seg, *label, *cnt, *bad32;  // segmentation map, root per pixel, pixels per root / NUMBER per root, badness
+    int* small;                      // [0] status word, [1] number of objects, [4 ..] block counts of the scan
+    int np, nsb;
+};
+int zm_ex_check(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_extract_params* params,
+                int max_objects, const zm_object* out_rows, const int* out_nwritten, const int* out_nfound);
+int zm_ex_planes(zm_ctx* ctx, int nx, int ny, int32_t* segm_dev, float* filtered_dev, zm_ex_bufs* b);
+void zm_ex_label(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, int nx, int ny,
+                 const zm_extract_params* params, const zm_ex_bufs* b);
+int zm_ex_recount(zm_ctx* ctx, const int* label, const zm_ex_bufs* b);
+void zm_ex_count_roots(zm_ctx* ctx, const int* label, int minarea, const zm_ex_bufs* b);
+void zm_ex_number(zm_ctx* ctx, const int* label, const float* img, const int32_t* flag, int nx, int ny,
+                  const zm_extract_params* params, int cap, int* seg, int* obj, const zm_ex_bufs* b);
+int zm_ex_rows(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_wcs* wcs,
+               const zm_extract_params* params, int n, const int* d_seg, const int* d_obj, const zm_ex_bufs* b,
+               zm_object* out_rows);
+int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* flag, int nx, int ny,
+               const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows, int32_t* out_segm,
+               float* out_filtered, int* out_nwritten, int* out_nfound, int* out_status, const zm_deblend_params* deblend,
+               int32_t* out_parent);

@@ -15,7 +15,8 @@ from . import _lib
 from ._lib import as_f32, as_i32, check, ptr, wcs_struct
 from .engine import Engine
 
-__all__ = ['CATALOG_COLUMNS', 'PARAM_COLUMNS', 'extract_params', 'measure_params', 'TooManyDetectionsError']
+__all__ = ['CATALOG_COLUMNS', 'PARAM_COLUMNS', 'extract_params', 'measure_params', 'deblend_params', 'deblend_settings',
+           'TooManyDetectionsError']
 
 # column of the catalog <- field of zm_object (include/zudsmi.h); columns that are not computed are absent
 CATALOG_COLUMNS = [('NUMBER', 'number', 'i4'), ('X_IMAGE', 'x_image', 'f8'), ('Y_IMAGE', 'y_image', 'f8'),
@@ -73,6 +74,46 @@ def measure_params(kron_fact=2.5, kron_min_radius=3.5, filter=True):
     return p
 
 
+DEBLEND_DEFAULTS = dict(nthresh=32, mincont=0.005)      # DEBLEND_NTHRESH, DEBLEND_MINCONT of sextractor.conf
+
+
+def deblend_settings(deblend=True):
+    """``None`` (no deblending) or dict(nthresh=, mincont=) from ``deblend=False | True | dict(nthresh=, mincont=)``.
+    ``nthresh`` must be a power of two in 2 .. 64 and ``mincont`` lie in [0, 1]; anything else raises ValueError."""
+    if deblend is None or deblend is False:
+        return None
+    kw = {} if deblend is True else dict(deblend)
+    unknown = set(kw) - set(DEBLEND_DEFAULTS)
+    if unknown:
+        raise ValueError(f'deblend: unknown keys {sorted(unknown)} (nthresh, mincont)')
+    nthresh, mincont = kw.get('nthresh', DEBLEND_DEFAULTS['nthresh']), float(kw.get('mincont', DEBLEND_DEFAULTS['mincont']))
+    if int(nthresh) != nthresh or not 2 <= int(nthresh) <= 64 or int(nthresh) & (int(nthresh) - 1):
+        raise ValueError(f'deblend: nthresh={nthresh!r} must be a power of two in 2 .. 64')
+    if not 0.0 <= mincont <= 1.0:
+        raise ValueError(f'deblend: mincont={mincont!r} must lie in [0, 1]')
+    return dict(nthresh=int(nthresh), mincont=mincont)
+
+
+def deblend_params(deblend=True):
+    """``None`` or the zm_deblend_params of ``deblend_settings(deblend)``."""
+    kw = deblend_settings(deblend)
+    if kw is None:
+        return None
+    p = _lib.zm_deblend_params()
+    _lib.lib().zm_deblend_params_default(C.byref(p))
+    p.nthresh, p.mincont = kw['nthresh'], kw['mincont']
+    return p
+
+
+def with_parent(tab, parent):
+    """``tab`` with a PARENT_NUMBER column (int32: the first-pass NUMBER of the object a row was part of)."""
+    out = np.zeros(len(tab), dtype=np.dtype(tab.dtype.descr + [('PARENT_NUMBER', 'i4')]))
+    for c in tab.dtype.names:
+        out[c] = tab[c]
+    out['PARENT_NUMBER'] = parent[:len(tab)]
+    return out.view(np.recarray)
+
+
 def _split_params(columns, params):
     """(extraction keywords, zm_measure_params or None) of a call's ``columns`` and keyword arguments."""
     if columns not in COLUMN_SETS:
@@ -115,7 +156,7 @@ def rows_to_table(rows, n):
     return tab.view(np.recarray)
 
 
-def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, segm, filtered):
+def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, segm, filtered, deblend=None):
     # the row array is kept between calls (12 MB at the default capacity: allocating and clearing it takes longer than
     # the extraction of a frame), one per calling thread: threads that share an engine do not share rows
     nrows = max(int(max_objects), 1)
@@ -125,13 +166,20 @@ def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_object
         rows = cache[threading.get_ident()] = (_lib.zm_object * nrows)()
     nw, nf, st = C.c_int(), C.c_int(), C.c_int()
     w = wcs_struct(wcs) if wcs is not None else None
+    if deblend is None:
+        check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
+                 int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st)), what)
+        return rows_to_table(rows, nw.value), nf.value, st.value
+    # fn is the deblending form of the entry point: two more arguments, one more column
+    parent = np.zeros(nrows, np.int32)
     check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
-             int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st)), what)
-    return rows_to_table(rows, nw.value), nf.value, st.value
+             int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st),
+             C.byref(deblend), ptr(parent)), what)
+    return with_parent(rows_to_table(rows, nw.value), parent), nf.value, st.value
 
 
 def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects=MAX_OBJECTS, full=False,
-                    columns='isophotal', **params):
+                    columns='isophotal', deblend=False, **params):
     """Object table (numpy record array, columns ``CATALOG_COLUMNS``) and segmentation map (int32, 0 = sky) of ``img``
     (background already subtracted) with per-pixel noise ``sigma``, bad-pixel map ``bad`` and flag plane ``flag``.
 
@@ -141,8 +189,13 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
 
     ``columns='param'``: the wide table (``PARAM_COLUMNS``: every column of sextractor.param) from a second pass,
     ``zm_extract_measure``; ``params`` may then carry kron_fact and kron_min_radius (PHOT_AUTOPARAMS), and ``full=True``
-    adds ``ext``, the rows of that pass with every intermediate value."""
+    adds ``ext``, the rows of that pass with every intermediate value.
+
+    ``deblend=True`` or ``dict(nthresh=, mincont=)``: multi-threshold deblending (``zm_extract_deblend``; DESIGN.md,
+    "Deblending").  Objects are numbered after the split, sub-objects of a split parent carry FLAGS bit 2, and the table
+    gains the column PARENT_NUMBER.  Where nothing splits, table and map are those of the default call."""
     params, mp = _split_params(columns, params)
+    db = deblend_params(deblend)
     img, sigma, flag = as_f32(img), as_f32(sigma), as_i32(flag)
     ny, nx = img.shape
     if sigma.shape != img.shape:
@@ -155,12 +208,16 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     p = extract_params(**params)
     segm = np.empty((ny, nx), np.int32)
     filt = np.empty((ny, nx), np.float32) if full else None
-    tab, nfound, status = _call(self, self.L.zm_extract, 'zm_extract', ptr(img), ptr(sigma), ptr(bad), ptr(flag), nx, ny,
-                                wcs, p, max_objects, ptr(segm), ptr(filt))
+    fn, what = (self.L.zm_extract, 'zm_extract') if db is None else (self.L.zm_extract_deblend, 'zm_extract_deblend')
+    tab, nfound, status = _call(self, fn, what, ptr(img), ptr(sigma), ptr(bad), ptr(flag), nx, ny,
+                                wcs, p, max_objects, ptr(segm), ptr(filt), db)
     ext = None
     if mp is not None:
+        first = tab
         tab, ext = _measure(self, self.L.zm_extract_measure, 'zm_extract_measure', ptr(img), ptr(sigma), ptr(bad),
                             ptr(segm), nx, ny, wcs, mp, len(tab))
+        if db is not None:
+            tab = with_parent(tab, first['PARENT_NUMBER'])
     if full and ext is not None:
         return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext)
     if full:
@@ -169,24 +226,30 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
 
 
 def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objects=MAX_OBJECTS, segm=None,
-                        columns='isophotal', **params):
+                        columns='isophotal', deblend=False, **params):
     """The same on device planes (addresses: float32 img, sigma; uint8 bad or None; int32 flag or None; ``segm``: an
     int32 device plane that takes the segmentation map, or None).  Returns (table, number found).
     ``columns='param'`` needs the segmentation map for its second pass: without ``segm`` a plane is allocated for the
-    call."""
+    call.  ``deblend``: as for ``Engine.extract``."""
     params, mp = _split_params(columns, params)
+    db = deblend_params(deblend)
     own = None
     if mp is not None and not segm:
         from . import hipmem
         own = hipmem.DeviceBuffer(int(nx) * int(ny) * 4)         # (freed when this call returns)
         segm = own.ptr
     p = extract_params(**params)
-    tab, nfound, _ = _call(self, self.L.zm_extract_dev, 'zm_extract_dev', int(img), int(sigma), int(bad) if bad else None,
+    fn, what = ((self.L.zm_extract_dev, 'zm_extract_dev') if db is None else
+                (self.L.zm_extract_deblend_dev, 'zm_extract_deblend_dev'))
+    tab, nfound, _ = _call(self, fn, what, int(img), int(sigma), int(bad) if bad else None,
                            int(flag) if flag else None, int(nx), int(ny), wcs, p, max_objects,
-                           int(segm) if segm else None, None)
+                           int(segm) if segm else None, None, db)
     if mp is not None:
+        first = tab
         tab, _ = _measure(self, self.L.zm_extract_measure_dev, 'zm_extract_measure_dev', int(img), int(sigma),
                           int(bad) if bad else None, int(segm), int(nx), int(ny), wcs, mp, len(tab))
+        if db is not None:
+            tab = with_parent(tab, first['PARENT_NUMBER'])
     return tab, nfound
 
 

@@ -55,10 +55,12 @@ class SubtractionJob(object):
     raised after the subtraction's files exist: the products are delivered all the same).
     ``rb_model`` (``realbogus.RBModel``, with ``detect``): ``cat`` carries the real / bogus score of the rows that reach
     the network and the ML cut at ``rb_cut`` or ``RB_CUT[fid]``; ``max_detections`` and ``stamps`` then see the rows that
-    survive that cut, as the reference's driver does."""
+    survive that cut, as the reference's driver does.
+    ``deblend`` (with ``detect``): False, True or dict(nthresh=, mincont=), the multi-threshold deblending of
+    ``DeviceSubtraction.candidates``; the result then carries ``deblend``, the settings used."""
 
     def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
-                 max_detections=50, rb_model=None, fid=None, rb_cut=None):
+                 max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False):
         if stamps and not detect:
             raise ValueError('stamps needs detect')
         if rb_model is not None:
@@ -66,6 +68,10 @@ class SubtractionJob(object):
             if not detect:
                 raise ValueError('rb_model needs detect')
             rb_cut_for(fid, rb_cut)                      # (raises when neither names a cut)
+        if deblend and not detect:
+            raise ValueError('deblend needs detect')
+        from .extract import deblend_settings
+        self.deblend = deblend_settings(deblend)         # (raises on settings the extractor refuses)
         self.rb_model, self.fid, self.rb_cut = rb_model, fid, rb_cut
         self.sci, self.ref, self.radec = sci, ref, radec
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag
@@ -170,7 +176,10 @@ def _detect(ch, job, out):
         if getattr(job, 'rb_model', None) is not None:
             rbkw = dict(rb_model=job.rb_model, sci=sci['img'], ref=ref['img'], fid=job.fid, rb_cut=job.rb_cut,
                         sci_flxscale=float(sci.get('flxscale', 1.0)))
-        cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'], **rbkw)
+        dbkw = {}
+        if getattr(job, 'deblend', None):
+            dbkw['deblend'] = out['deblend'] = job.deblend
+        cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'], **rbkw, **dbkw)
     except _lib.ZMError as exc:
         out['cat'], out['detect_error'] = None, str(exc)
         return

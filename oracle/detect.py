@@ -12,11 +12,15 @@ here is the pixel arithmetic, as chosen conventions:
   ``nmax`` brightest are used (sorted by peak, then y, then x);
 * FWHM = 2.3548 sigma from adaptive Gaussian-weighted second moments: weight
   ``exp(-r^2 / 2 s_w^2)`` about the current centroid, measured ``m2 = sum(w I r^2) / (2 sum(w I))``,
-  de-weighted ``sigma^2 = 1 / (1 / m2 - 1 / s_w^2)``, ``s_w^2 <- sigma^2`` until it settles
-  (exact for a Gaussian star whatever the start);
+  de-weighted ``sigma^2 = 1 / (1 / m2 - 1 / s_w^2)``, ``s_w^2 <- sigma^2`` until two rounds agree
+  to 1e-8 or 25 rounds are up.  For the integrals of a Gaussian one round would be exact whatever
+  the start; for the pixel sums it is not: the iteration converges linearly, each step about half
+  the one before (a clean FWHM 2.5 star stops at round 16), and an undersampled star (FWHM 1.5 px
+  and below) does not converge at all (DESIGN.md, "Seeing estimate");
 * seeing = median of the finite FWHMs (``np.nanmedian`` as ``zuds/seeing.py:113``);
 * negative-pixel cut exactly as ``filterobjects.py:155-195`` except that cutouts are clipped at
-  the frame edges (numpy's negative slice indices wrap around there).
+  the frame edges (numpy's negative slice indices wrap around there) and that a position which
+  is not finite has no cutout and so no hit.
 """
 import numpy as np
 
@@ -50,6 +54,7 @@ def star_fwhm(img, x, y, half=10, maxit=25):
     ny, nx = img.shape
     j0, j1 = max(y - half, 0), min(y + half + 1, ny)
     i0, i1 = max(x - half, 0), min(x + half + 1, nx)
+    j1, i1 = max(j1, j0), max(i1, i0)       # a window that misses the frame is empty (a negative stop would wrap)
     jj, ii = np.mgrid[j0:j1, i0:i1]
     I = img[j0:j1, i0:i1]
     cx, cy, s2 = float(x), float(y), 4.0
@@ -91,6 +96,8 @@ def negpix(img, x, y, med, sig, half=5):
     s = (img - np.float32(med)) / np.float32(sig)
     out = np.zeros(len(x), dtype=np.int32)
     for k, (xs, ys) in enumerate(zip(x, y)):
+        if not (np.isfinite(xs) and np.isfinite(ys)):
+            continue                              # no cutout: no hit (both GPU routes say the same)
         xc, yc = int(np.round(xs)) - 1, int(np.round(ys)) - 1
         hit = False
         for j in range(max(yc - half, 0), min(yc + half, ny - 1) + 1):

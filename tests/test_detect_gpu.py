@@ -61,6 +61,7 @@ def test_fwhm_matches_oracle_and_truth(engine):
         ref = np.array([odet.star_fwhm(img, int(x), int(y), 10) for x, y in zip(xs, ys)])
         np.testing.assert_allclose(fw, ref[:, 0], rtol=1e-9, equal_nan=True)
         np.testing.assert_allclose(cx, ref[:, 1], rtol=0, atol=1e-8)
+        np.testing.assert_allclose(cy, ref[:, 2], rtol=0, atol=1e-8)
         assert abs(np.nanmedian(fw) / fwhm - 1) < 0.03
 
 

@@ -100,7 +100,11 @@ __global__ void k_negpix(const float* __restrict__ img, int nx, int ny, int npos
                          float sig, int half, int32_t* __restrict__ bad) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= npos) return;
-    const int xc = (int)rint(xs[k]) - 1, yc = (int)rint(ys[k]) - 1;     // np.round: half to even
+    // a position that is not finite has no cutout; a finite one is clamped while still double, as k_candidate_cuts
+    // does: further than 64 pixels outside the frame no cutout pixel is inside it, wherever the centre lies
+    if (!isfinite(xs[k]) || !isfinite(ys[k])) { bad[k] = 0; return; }
+    const int xc = (int)fmin(fmax(rint(xs[k]), -64.0), nx + 64.0) - 1;  // np.round: half to even
+    const int yc = (int)fmin(fmax(rint(ys[k]), -64.0), ny + 64.0) - 1;
     int b = 0;
     for (int j = yc - half; j <= yc + half && !b; ++j)
         for (int i = xc - half; i <= xc + half && !b; ++i) {

@@ -22,6 +22,7 @@ ISOLATION = 5         # pixels: a star is the maximum of its 11 x 11 box
 BORDER = 12
 HALF = 10             # moments window: 21 x 21
 NSIGMA = 30.0         # detection threshold above the background, in background sigmas
+CAP = 65536           # candidates taken per pass; a fuller list doubles the threshold and looks again
 
 
 def measure_seeing(data, bad=None, saturate=None, engine=None):
@@ -36,7 +37,7 @@ def measure_seeing(data, bad=None, saturate=None, engine=None):
     lo = float(NSIGMA * max(bsig, 1e-6))
     hi = float(0.5 * saturate - bmean) if saturate else 3.0e38
     bad8 = None if bad is None else np.ascontiguousarray(bad).astype(np.uint8)
-    cap = 65536
+    cap = CAP
     xs = np.empty(cap, np.int32)
     ys = np.empty(cap, np.int32)
     pk = np.empty(cap, np.float32)
@@ -81,7 +82,7 @@ def measure_seeing_dev(img, bad=None, saturate=None, engine=None):
     bmean, bsig = stats[0], stats[1]
     lo = float(NSIGMA * max(bsig, 1e-6))
     hi = float(0.5 * saturate - bmean) if saturate else 3.0e38
-    cap = 65536
+    cap = CAP
     xs = np.empty(cap, np.int32)
     ys = np.empty(cap, np.int32)
     pk = np.empty(cap, np.float32)

@@ -530,7 +530,7 @@ typedef struct zm_object {
     int32_t number;          /* NUMBER */
     int32_t npix;            /* ISOAREA_IMAGE */
     int32_t xmin, xmax, ymin, ymax;   /* XMIN_IMAGE .. YMAX_IMAGE */
-    int32_t flags;           /* FLAGS: 2 deblended (zm_extract_deblend only), 4 saturated, 8 on the frame border, 16 aperture incomplete */
+    int32_t flags;           /* FLAGS: 2 deblended (with deblending only), 4 saturated, 8 on the frame border, 16 aperture incomplete */
     int32_t flags_weight;    /* FLAGS_WEIGHT: 1 = a bad pixel touches the object */
     int32_t imaflags_iso;    /* IMAFLAGS_ISO: OR of the flag plane over the object */
     int32_t first;           /* 0-based linear index of the object's first pixel in raster order */
@@ -568,8 +568,8 @@ int zm_extract(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
  * points run the same first pass and then split every object whose tree of nthresh exponentially spaced levels has at
  * least two significant branches ("Deblending"; restated in tests/deblend_ref.py).  Objects, split or not, are
  * renumbered 1 .. n in raster order of their first pixel and measured on their own pixels; the sub-objects of a split
- * parent carry FLAGS bit 2.  Where nothing splits, rows and map equal those of zm_extract bit for bit.  There is no
- * CLEAN pass: the mincont test is the only guard against shredding. */
+ * parent carry FLAGS bit 2.  Where nothing splits, rows and map equal those of zm_extract bit for bit.  The CLEAN pass
+ * that folds shreds back is a step of its own (zm_extract_clean, below). */
 typedef struct zm_deblend_params {
     int32_t nthresh;         /* DEBLEND_NTHRESH (32): a power of two in 2 .. 64 */
     int32_t pad_;
@@ -592,6 +592,51 @@ int zm_extract_deblend(zm_ctx* ctx, const float* img, const float* sigma, const 
                        const zm_extract_params* params, int max_objects, zm_object* out_rows,
                        int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
                        int* out_status, const zm_deblend_params* deblend, int32_t* out_parent);
+
+/* ---- source extraction with the CLEAN pass (opt-in) --------------------------- */
+/* CLEAN Y / CLEAN_PARAM of sextractor.conf.  The entry points above and their results are what they were.  These run the
+ * same passes (deblend == NULL: no deblending), then let every object be absorbed by the neighbour whose Moffat-like wing
+ * amp (1 + alpha q)^-param, as high as the detection threshold at the neighbour's isophotal area, exceeds what the object
+ * holds above its local threshold on its detect_minarea-th brightest pixel ("CLEAN"; restated in
+ * tests/clean_ref.py).  One round on the quantities from before any merge; an absorbed object still absorbs; every object
+ * ends at the root of its chain.  Merged objects are renumbered 1 .. n in raster order of their first pixel and measured
+ * on the union of their pixels.  Where nothing is absorbed, rows and map equal those of the call without CLEAN bit for
+ * bit.  FLAGS bit 2 and out_parent follow the rule of zm_extract_deblend on the final rows: a parent that was split keeps
+ * bit 2 even where CLEAN folds all its pieces back. */
+typedef struct zm_clean_params {
+    double param;            /* CLEAN_PARAM (1.0): the wing's exponent, finite, in [0.1, 10] */
+} zm_clean_params;
+void zm_clean_params_default(zm_clean_params* p);
+
+#define ZM_EXTRACT_CLEAN 4       /* status bit: a chain of absorptions passed its bound (results are not to be used) */
+
+/* The arguments of zm_extract_deblend_dev (deblend and out_parent may be NULL), then the CLEAN parameters and out_nmerged
+ * (host array of max_objects int32, or NULL): the objects from before CLEAN that a row holds, 1 = untouched.  CLEAN sees
+ * every object of the pass before, whatever max_objects is: max_objects truncates the final table alone. */
+int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                         const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                         const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                         int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
+                         int* out_status, const zm_deblend_params* deblend, const zm_clean_params* clean,
+                         int32_t* out_parent, int32_t* out_nmerged);
+/* The same with host planes. */
+int zm_extract_clean(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                     const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                     const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                     int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
+                     int* out_status, const zm_deblend_params* deblend, const zm_clean_params* clean,
+                     int32_t* out_parent, int32_t* out_nmerged);
+/* The per-object sums (k_cl_stats) of the last zm_extract_clean[_dev] call on this context, for the first
+ * min(max_n, *out_n) objects from before CLEAN: F (float64 sum of the filtered values), T (threshold at the peak pixel)
+ * and m (the detect_minarea-th largest excess over the local threshold).  Host arrays; any of them may be NULL. */
+int zm_extract_clean_stats(zm_ctx* ctx, int max_n, double* fdflux, float* dthresh, float* mthresh, int* out_n);
+/* The decision alone, on host arrays of n objects: rows (number == index + 1; x_image, y_image, a_image, b_image, x2, y2,
+ * xy, npix and first are read), fdflux = F, dthresh = T, mthresh = m, minarea = DETECT_MINAREA (every npix is at least
+ * that).  out_into[j]: the NUMBER of the object that absorbs j, 0 for none; out_root[j]: the NUMBER at the end of j's
+ * chain (its own where it is not absorbed).  Either may be NULL. */
+int zm_clean_decide(zm_ctx* ctx, int n, const zm_object* rows, const double* fdflux, const float* dthresh,
+                    const float* mthresh, int minarea, const zm_clean_params* clean, int32_t* out_into,
+                    int32_t* out_root);
 
 /* ---- source extraction, second pass: the Kron and windowed columns of sextractor.param ---- */
 /* Opt-in: zm_extract and its table are what they were.  Measures, for rows zm_extract wrote, the columns of

@@ -6,7 +6,7 @@ subtractions as one batch of launches on each of J lanes (``nightly.SubtractionP
 ``--fit-batch 0``: J separate subtractions in flight).
 
 usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch B] [--batch FRAMES] [--nreg-side N]
-                    [--detect [--stamps] [--deblend] [--rb-model BASE [--rb-cut X]] [--associate [--stars F]]]
+                    [--detect [--stamps] [--deblend] [--clean [--clean-param X]] [--rb-model BASE [--rb-cut X]] [--associate [--stars F]]]
 
 * ``images.txt``: science image paths (``*sciimg.fits``; the mask is ``*mskimg.fits``; a
   ``.weight.fits`` sibling is required: 1 / rms^2, 0 on bad pixels).  The list is sharded over
@@ -26,6 +26,8 @@ Products per image, with the reference's names: ``sub.<sci>_<ref>.fits``, ``.rms
 its ``GOODCUT == 1`` rows in the layout of ``dosub.py --stamps``; more than 50 such rows: no stamps file (the
 reference's TooManyDetectionsError).  ``--deblend`` (needs ``--detect``): the extraction deblends (``DEBLEND_NTHRESH`` 32,
 ``DEBLEND_MINCONT`` 0.005; DESIGN.md "Deblending"): the tables carry ``PARENT_NUMBER`` and the headers say ``ZMDEBLND = T``.
+``--clean`` (needs ``--detect``): the extraction ends with the CLEAN pass (``CLEAN_PARAM`` 1.0, or ``--clean-param X``;
+DESIGN.md "CLEAN"): the tables carry ``NMERGED`` and the headers say ``ZMCLEAN = T`` and ``ZMCLNPAR``.
 ``--associate`` (needs ``--detect``): once the pool has drained, the night's
 in-memory tables go through ``zuds.associate`` (the job of ``nersc/makesources.py``; ``scripts/makesources.py`` does the
 same from the ``sub.*.cat`` files) and ``<images>.sources.txt`` / ``<images>.sources.det.txt`` are written next to the
@@ -123,6 +125,7 @@ def write_detections(out, hdr, ref, res):
     cat.map_to_local_file(out.replace('.fits', '.cat'))
     cat.data, cat.header, cat.header_comments = res['cat'], dict(hdr), {}
     cat.deblend = res.get('deblend')
+    cat.clean = res.get('clean')
     cat.save()
     if res.get('too_many'):
         print(f'Error: {int((res["cat"]["GOODCUT"] == 1).sum())} detections (>{MAX_DETS}) '
@@ -190,6 +193,9 @@ def main(argv=None):
     ap.add_argument('--stamps', action='store_true', help='with --detect: write sub.*.stamps.fits, the thumbnails of the detections')
     ap.add_argument('--deblend', action='store_true', help='with --detect: multi-threshold deblending (DEBLEND_NTHRESH 32, '
                                                            'DEBLEND_MINCONT 0.005); the catalogs say ZMDEBLND = T')
+    ap.add_argument('--clean', action='store_true', help='with --detect: the CLEAN pass (CLEAN_PARAM 1.0); the catalogs say '
+                                                         'ZMCLEAN = T')
+    ap.add_argument('--clean-param', type=float, help='with --clean: CLEAN_PARAM, in [0.1, 10]')
     ap.add_argument('--rb-model', help='with --detect: BASE of BASE.architecture.json + BASE.weights.npz, the real / bogus '
                                        'network the candidate filter ends with (realbogus.load_model)')
     ap.add_argument('--rb-cut', type=float, help='with --rb-model: the score below which a candidate is cut; default '
@@ -207,6 +213,16 @@ def main(argv=None):
     if args.deblend and not args.detect:
         print('--deblend needs --detect', file=sys.stderr)
         return 2
+    if (args.clean or args.clean_param is not None) and not (args.detect and args.clean):
+        print('--clean needs --detect (and --clean-param needs --clean)', file=sys.stderr)
+        return 2
+    clean = args.clean
+    if args.clean_param is not None:
+        try:
+            clean = zuds.clean_settings(dict(param=args.clean_param))
+        except ValueError as exc:
+            print(f'--clean-param: {exc}', file=sys.stderr)
+            return 2
     if (args.rb_model or args.rb_cut is not None) and not args.detect:
         print('--rb-model needs --detect', file=sys.stderr)
         return 2
@@ -235,7 +251,7 @@ def main(argv=None):
     try:
         done = run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side,
                          detect=args.detect, stamps=args.stamps, rb_model=rb_model, rb_cut=args.rb_cut, tables=tables,
-                         deblend=args.deblend)
+                         deblend=args.deblend, clean=clean)
     finally:
         pool.close()
         ring.close()
@@ -261,7 +277,7 @@ def make_sources(tables, prefix, stars=None, engine=None):
 
 
 def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False, rb_model=None,
-              rb_cut=None, tables=None, deblend=False):
+              rb_cut=None, tables=None, deblend=False, clean=False):
     """The images of this rank against one reference.  The files of batch b + 1 are read, sent and decoded by the
     ring (fitsring.FITSRing: reader threads, copy stream) while the pool subtracts batch b; the products of batch b
     are encoded on the device, copied back on a third stream and written by the ring's writer threads while
@@ -322,7 +338,7 @@ def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, dete
                     # the filter id as image.py reads it; a frame without the card and no --rb-cut fails here (ValueError)
                     rbkw = dict(rb_model=rb_model, rb_cut=rb_cut, fid=hdr.get('FID', hdr.get('FILTERID')))
                 job = nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
-                                             stamps=stamps, max_detections=MAX_DETS, deblend=deblend, **rbkw)
+                                             stamps=stamps, max_detections=MAX_DETS, deblend=deblend, clean=clean, **rbkw)
             except Exception:
                 # (the reference's drivers: try / except per image, scripts/dosub.py:205-213)
                 traceback.print_exception(*sys.exc_info())

@@ -2,7 +2,8 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns] [--deblend] [--rb-model BASE [--rb-cut X]]]
+usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns] [--deblend] [--clean [--clean-param X]]
+                                        [--rb-model BASE [--rb-cut X]]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
@@ -14,6 +15,8 @@ once the detections have been filtered (``PipelineRegionFile.from_catalog``: gre
 elsewhere).
 With ``--deblend`` (needs ``--detect``) the extraction deblends (``DEBLEND_NTHRESH`` 32, ``DEBLEND_MINCONT`` 0.005): the
 catalog's header says ``ZMDEBLND = T`` and its table carries ``PARENT_NUMBER``.
+With ``--clean`` (needs ``--detect``) the extraction ends with the CLEAN pass (``CLEAN_PARAM`` 1.0, or ``--clean-param X``):
+the catalog's header says ``ZMCLEAN = T`` and ``ZMCLNPAR``, and its table carries ``NMERGED``.
 With ``--stamps`` (needs ``--detect``) every detection also gets its three thumbnails - difference, new and reference
 image on the reference image's grid (``Thumbnail.from_detections``, dosub.py:133-150) - and ``sub.*.stamps.fits`` is
 written next to the catalog: the zero-filled blocks ``[n, 3, 63, 63]`` (sub, new, ref) and a table with ``ra``, ``dec``,
@@ -76,7 +79,7 @@ def write_stamps(sub, detections, stamps, size=None):
 
 
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
-           rb_cut=None, deblend=False):
+           rb_cut=None, deblend=False, clean=False):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -119,7 +122,7 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
     if detect:
         catstart = time.time()
         cat = zuds.PipelineFITSCatalog.from_image(sub, columns='param' if param_columns else 'isophotal',
-                                                   deblend=deblend)
+                                                   deblend=deblend, clean=clean)
         catstop = time.time()
         print(f'cat: {catstop - catstart:.2f} sec to make catalog for {sub.basename}', flush=True)
         dstart = time.time()
@@ -169,9 +172,16 @@ def main(argv):
     if deblend and not detect:
         print('--deblend needs --detect', file=sys.stderr)
         return 2
+    clean = '--clean' in argv
+    if (clean or '--clean-param' in argv) and not detect:
+        print('--clean needs --detect', file=sys.stderr)
+        return 2
+    if '--clean-param' in argv and not clean:
+        print('--clean-param needs --clean', file=sys.stderr)
+        return 2
     argv = list(argv)
     rb_model = rb_cut = None
-    for flag in ('--rb-model', '--rb-cut'):
+    for flag in ('--rb-model', '--rb-cut', '--clean-param'):
         if flag in argv:
             k = argv.index(flag)
             if k + 1 >= len(argv):
@@ -181,6 +191,12 @@ def main(argv):
             del argv[k:k + 2]
             if flag == '--rb-model':
                 rb_model = value
+            elif flag == '--clean-param':
+                try:
+                    clean = zuds.clean_settings(dict(param=float(value)))
+                except ValueError as exc:
+                    print(f'--clean-param: {exc}', file=sys.stderr)
+                    return 2
             else:
                 rb_cut = float(value)
     if (rb_model or rb_cut is not None) and not detect:
@@ -191,7 +207,7 @@ def main(argv):
         return 2
     if rb_model:
         rb_model = zuds.load_model(rb_model)
-    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend')]
+    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend', '--clean')]
     infile = args[0]
     refname = args[1]
     subclass = zuds.SingleEpochSubtraction
@@ -200,7 +216,7 @@ def main(argv):
     for fn in imgs:
         try:
             do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
-                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend)
+                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

@@ -16,6 +16,13 @@ events, per call:
   ``deblend_over_default`` is its ratio to ``extract_ms`` of the same run, ``objects_deblend`` what it finds;
 * ``crowded_ms`` / ``crowded_deblend_ms``  both calls on a crowded field of ``--crowded-size`` px a side: 3000 stars under
   noise 1, a third of them companions 3 .. 6 px from another star (``crowded_objects`` / ``crowded_objects_deblend``);
+* ``extract_clean_ms`` / ``extract_deblend_clean_ms``  the default and the deblending call with ``clean=True`` on the
+  bench's epoch (every object of the pass before numbered and measured, ``k_cl_stats``, the decision, and where anything
+  is absorbed a second numbering and measurement); ``objects_clean`` / ``objects_deblend_clean`` what they find;
+  ``crowded_clean_ms`` / ``crowded_deblend_clean_ms`` the same on the crowded field;
+* ``decide_ms``    ``zm_clean_decide`` alone (model on the host, upload, ``k_cl_pairs``, ``k_cl_resolve``, two arrays back) on
+  synthetic tables of 10^3, 10^4 and 10^5 rows at the surface density of the crowded field (``decide_absorbed``: how many
+  rows were absorbed); the all-pairs kernel is quadratic in the rows;
 * ``copy_ms``      a float4 copy (``zm_copy_probe_dev``) that moves the bytes of the planes the extractor has to touch
   at least once: image, noise, flag plane, segmentation map (4 B per pixel each) and the bad-pixel map (1 B).  The copy
   cycles through four source / destination pairs (640 MB in all at the default size), more than the 256 MB last-level
@@ -103,6 +110,14 @@ def main():
         tab, nfound, _ = sub.extract(deblend=True)
         found['deblend'] = nfound
 
+    def extract_clean():
+        tab, nfound, _ = sub.extract(clean=True)
+        found['clean'] = nfound
+
+    def extract_deblend_clean():
+        tab, nfound, _ = sub.extract(deblend=True, clean=True)
+        found['deblend_clean'] = nfound
+
     # the crowded field: 2000 stars and 1000 companions 3 .. 6 px from one of them, noise 1
     csize = args.crowded_size
     rng = np.random.default_rng(31)
@@ -120,6 +135,34 @@ def main():
 
     def crowded_deblend():
         tab, found['crowded_deblend'] = eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize, deblend=True)
+
+    def crowded_clean():
+        tab, found['crowded_clean'] = eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize, clean=True)
+
+    def crowded_deblend_clean():
+        tab, found['crowded_deblend_clean'] = eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize,
+                                                              deblend=True, clean=True)
+
+    def decide_table(n):
+        """n synthetic rows at the crowded field's surface density (1505 objects on 1024 x 1024): one in ten bright and
+        extended, the rest faint and compact."""
+        trng = np.random.default_rng(1000 + n)
+        side = csize * np.sqrt(n / 1505.0)
+        rows = np.zeros(n, np.dtype(z._lib.zm_object))
+        rows['number'] = np.arange(1, n + 1)
+        rows['x_image'], rows['y_image'] = trng.uniform(1, side, n), trng.uniform(1, side, n)
+        big = trng.random(n) < 0.1
+        a = np.where(big, trng.uniform(3.0, 8.0, n), trng.uniform(0.6, 1.5, n))
+        b = a * trng.uniform(0.5, 1.0, n)
+        th = trng.uniform(-np.pi / 2, np.pi / 2, n)
+        rows['x2'] = a * a * np.cos(th) ** 2 + b * b * np.sin(th) ** 2
+        rows['y2'] = a * a * np.sin(th) ** 2 + b * b * np.cos(th) ** 2
+        rows['xy'] = (a * a - b * b) * np.sin(th) * np.cos(th)
+        rows['a_image'], rows['b_image'] = a, b
+        rows['npix'] = np.maximum(5, (np.pi * a * b * trng.uniform(2.0, 4.0, n)).astype(np.int32))
+        rows['first'] = trng.permutation(n).astype(np.int32)
+        F = np.where(big, 10 ** trng.uniform(4.0, 6.0, n), 10 ** trng.uniform(1.8, 3.0, n)) * rows['npix'] / 10.0
+        return rows, F, np.full(n, 6.0, np.float32), trng.uniform(0.5, 6.0, n).astype(np.float32)
 
     nbytes = (17 * size * size // 2) // 16 * 16
     pairs = [(torch.zeros(nbytes, dtype=torch.uint8, device=device), torch.empty(nbytes, dtype=torch.uint8, device=device))
@@ -151,6 +194,21 @@ def main():
     d_med, d_min = clock(extract_deblend)
     cr_med, _ = clock(crowded)
     crd_med, _ = clock(crowded_deblend)
+    ec_med, ec_min = clock(extract_clean)
+    edc_med, edc_min = clock(extract_deblend_clean)
+    crc_med, _ = clock(crowded_clean)
+    crdc_med, _ = clock(crowded_deblend_clean)
+    decide_ms, decide_absorbed = {}, {}
+    keep_steps = (args.steps, args.warmup)
+    for n in (1000, 10000, 100000):
+        table = decide_table(n)
+
+        def decide():
+            into, _ = eng.clean_decide(*table)
+            decide_absorbed[str(n)] = int((into > 0).sum())
+        args.steps, args.warmup = (5, 1) if n >= 100000 else keep_steps
+        decide_ms[str(n)] = round(clock(decide)[0], 4)
+    args.steps, args.warmup = keep_steps
     c_med, c_min = clock(copy)
     flat = torch.full((size, size), 100.0, dtype=torch.float32, device=device)
     one = torch.ones((size, size), dtype=torch.float32, device=device)
@@ -171,6 +229,12 @@ def main():
                deblend_over_default=round(d_med / e_med, 2), crowded_size=csize, crowded_ms=round(cr_med, 4),
                crowded_deblend_ms=round(crd_med, 4), crowded_objects=found.get('crowded'),
                crowded_objects_deblend=found.get('crowded_deblend'),
+               extract_clean_ms=round(ec_med, 4), extract_clean_ms_min=round(ec_min, 4), objects_clean=found.get('clean'),
+               extract_deblend_clean_ms=round(edc_med, 4), extract_deblend_clean_ms_min=round(edc_min, 4),
+               objects_deblend_clean=found.get('deblend_clean'), crowded_clean_ms=round(crc_med, 4),
+               crowded_deblend_clean_ms=round(crdc_med, 4), crowded_objects_clean=found.get('crowded_clean'),
+               crowded_objects_deblend_clean=found.get('crowded_deblend_clean'), decide_ms=decide_ms,
+               decide_absorbed=decide_absorbed,
                copy_ms=round(c_med, 4), copy_bytes_per_pixel=17,
                extract_over_subtract=round(e_med / s_med, 3), extract_over_copy=round(e_med / c_med, 2))
     line = json.dumps(out)

@@ -103,6 +103,10 @@ class zm_deblend_params(C.Structure):
     _fields_ = [('nthresh', C.c_int32), ('pad_', C.c_int32), ('mincont', C.c_double)]
 
 
+class zm_clean_params(C.Structure):
+    _fields_ = [('param', C.c_double)]
+
+
 class zm_object(C.Structure):
     """One row of the object table of ``zm_extract`` (include/zudsmi.h)."""
     _fields_ = [('number', C.c_int32), ('npix', C.c_int32), ('xmin', C.c_int32), ('xmax', C.c_int32),
@@ -176,6 +180,7 @@ STAMP_MAX, STAMP_PLANES_MAX = 256, 8                   # ZM_STAMP_MAX, ZM_STAMP_
 STAMP_NOT_FINITE, STAMP_NO_OVERLAP = 1, 2              # zm_stamp_origin status words
 EXTRACT_CHAIN = 1                                      # zm_extract status bit (ZM_EXTRACT_CHAIN)
 EXTRACT_DEBLEND = 2                                    # zm_extract_deblend status bit (ZM_EXTRACT_DEBLEND)
+EXTRACT_CLEAN = 4                                      # zm_extract_clean status bit (ZM_EXTRACT_CLEAN)
 HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4          # zm_hp_info.status bits (include/zudsmi.h)
 
 
@@ -289,6 +294,17 @@ _SIGS = {
     'zm_extract_deblend': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
                                      C.POINTER(zm_extract_params), C.c_int, _P, _P, _P, C.POINTER(C.c_int),
                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(zm_deblend_params), _P]),
+    'zm_clean_params_default': (None, [C.POINTER(zm_clean_params)]),
+    'zm_extract_clean_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
+                                       C.POINTER(zm_extract_params), C.c_int, _P, _P, _P, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(zm_deblend_params),
+                                       C.POINTER(zm_clean_params), _P, _P]),
+    'zm_extract_clean': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
+                                   C.POINTER(zm_extract_params), C.c_int, _P, _P, _P, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(zm_deblend_params),
+                                   C.POINTER(zm_clean_params), _P, _P]),
+    'zm_extract_clean_stats': (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_int)]),
+    'zm_clean_decide': (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.POINTER(zm_clean_params), _P, _P]),
     'zm_measure_params_default': (None, [C.POINTER(zm_measure_params)]),
     'zm_extract_measure_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
                                          C.POINTER(zm_measure_params), C.c_int, _P, _P]),

@@ -4,7 +4,9 @@
 SExtractor; the table holds the columns that are computed (``extract.CATALOG_COLUMNS``) and no others.  On disk a
 catalog is a FITS_LDAC file, as the reference asks SExtractor for (``catalog_type='FITS_LDAC'``): the object table is
 HDU 2.  ``from_image(..., columns='param')`` asks for the wide table (``extract.PARAM_COLUMNS``: every column of
-``sextractor.param``), which ``PipelineRegionFile.from_catalog`` needs.
+``sextractor.param``), which ``PipelineRegionFile.from_catalog`` needs.  ``from_image(..., deblend=, clean=)`` pass the
+two opt-in steps of the extractor on (``Engine.extract``); the table's header says which ran (``ZMDEBLND``, ``ZMCLEAN`` and
+their parameters), and ``from_file`` reads that back into ``cat.deblend`` / ``cat.clean``.
 """
 from pathlib import Path
 
@@ -16,7 +18,8 @@ from .file import File, UnmappedFileError
 
 __all__ = ['PipelineFITSCatalog', 'PipelineRegionFile']
 
-# what the extraction behind a catalog did not do, stated in its header (a catalog made with deblend=: header_cards)
+# what the extraction behind a catalog did not do, stated in its header (a catalog made with deblend= or clean=:
+# header_cards; the comments are those of the version that had neither step, kept so that a default catalog's bytes stay)
 HEADER_CARDS = [('ZMDEBLND', False, 'multi-threshold deblending (not in this version)'),
                 ('ZMCLEAN', False, 'CLEAN pass (not in this version)')]
 
@@ -24,13 +27,16 @@ HEADER_CARDS = [('ZMDEBLND', False, 'multi-threshold deblending (not in this ver
 WIDE_CARDS = [('ZMMASKTY', 'NONE', 'MASK_TYPE of the Kron and windowed sums')]
 
 
-def header_cards(deblend=None):
+def header_cards(deblend=None, clean=None):
     """The cards every catalog's header states the extractor's steps with; ``deblend``: None, or the
-    dict(nthresh=, mincont=) the catalog was made with."""
-    if not deblend:
-        return list(HEADER_CARDS)
-    return [('ZMDEBLND', True, 'multi-threshold deblending'), ('ZMDBNTHR', int(deblend['nthresh']), 'DEBLEND_NTHRESH'),
-            ('ZMDBMINC', float(deblend['mincont']), 'DEBLEND_MINCONT')] + HEADER_CARDS[1:]
+    dict(nthresh=, mincont=) the catalog was made with; ``clean``: None, or its dict(param=)."""
+    cards = list(HEADER_CARDS)
+    if deblend:
+        cards[:1] = [('ZMDEBLND', True, 'multi-threshold deblending'), ('ZMDBNTHR', int(deblend['nthresh']), 'DEBLEND_NTHRESH'),
+                     ('ZMDBMINC', float(deblend['mincont']), 'DEBLEND_MINCONT')]
+    if clean:
+        cards[-1:] = [('ZMCLEAN', True, 'CLEAN pass'), ('ZMCLNPAR', float(clean['param']), 'CLEAN_PARAM')]
+    return cards
 
 
 # the two lines every region file starts with (ds9: global properties, then the coordinate system)
@@ -74,13 +80,14 @@ class PipelineFITSCatalog(File):
     header_comments = None
     image = None
     deblend = None                # dict(nthresh=, mincont=) of a catalog made with deblending
+    clean = None                  # dict(param=) of a catalog made with the CLEAN pass
 
     @classmethod
-    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal', deblend=False):
+    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal', deblend=False, clean=False):
         from .image import CalibratableImageBase
         if not isinstance(image, CalibratableImageBase):
             raise ValueError('Image is not an instance of CalibratableImage.')
-        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns, deblend=deblend)
+        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns, deblend=deblend, clean=clean)
         cat = image.catalog
         for prop in GROUP_PROPERTIES:
             setattr(cat, prop, getattr(image, prop, None))
@@ -115,6 +122,8 @@ class PipelineFITSCatalog(File):
         self._data, self.table_header, self.header, self.header_comments = _fits.read_ldac(self.local_path)
         if self.table_header.get('ZMDEBLND') is True:
             self.deblend = dict(nthresh=int(self.table_header['ZMDBNTHR']), mincont=float(self.table_header['ZMDBMINC']))
+        if self.table_header.get('ZMCLEAN') is True:
+            self.clean = dict(param=float(self.table_header['ZMCLNPAR']))
 
     def save(self):
         try:
@@ -124,7 +133,7 @@ class PipelineFITSCatalog(File):
             self.map_to_local_file(f)
         wide = 'FLUX_AUTO' in (self.data.dtype.names or ())
         _fits.write_ldac(f, self.data, self.header or {}, self.header_comments or {},
-                         extra=header_cards(self.deblend) + (WIDE_CARDS if wide else []))
+                         extra=header_cards(self.deblend, self.clean) + (WIDE_CARDS if wide else []))
 
     def kill_flagged(self):
         """Drop the detections with a bad IMAFLAGS_ISO or a bad pixel next to them (``zuds/catalog.py:132-142``); a

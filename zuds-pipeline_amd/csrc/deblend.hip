@@ -352,19 +352,104 @@ extern "C" void zm_deblend_params_default(zm_deblend_params* p) {
     p->mincont = 0.005;
 }
 
+// The split stage: numbers the first pass in full (n1 > 0 objects: map and table of their own), splits every object that
+// can split, writes the new roots into b->label and leaves pixels per root and the number of objects in b->cnt / b->small[1].
+int zm_db_split(zm_ctx* ctx, const float* img, const float* sigma, const int32_t* flag, int nx, int ny,
+                const zm_extract_params* params, const zm_deblend_params* deblend, int n1, const zm_ex_bufs* b, int** out_seg1,
+                int** out_split) {
+    const int np = b->np, minarea = params->detect_minarea, N = deblend->nthresh;
+    int nroots = 0;
+    while ((1 << nroots) < N) ++nroots;
+    int *d_seg1 = nullptr, *d_obj1 = nullptr, *d_split = nullptr;
+    // the first pass in full: its map and its table, every object of it
+    ZM_TRY(ctx->get("db_seg1", (size_t)np * 4, (void**)&d_seg1));
+    ZM_TRY(ctx->get("db_obj1", (size_t)(n1 + 1) * EX_OI * 4, (void**)&d_obj1));
+    ZM_TRY(ctx->get("db_split", (size_t)n1 * 4, (void**)&d_split));
+    zm_ex_number(ctx, b->label, img, flag, nx, ny, params, n1, d_seg1, d_obj1, b);
+    ZM_HIP(hipMemsetAsync(d_split, 0, (size_t)n1 * 4, ctx->stream));
+    std::vector<int> oi((size_t)n1 * EX_OI);
+    ZM_HIP(hipMemcpyAsync(oi.data(), d_obj1, oi.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZM_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<db_cand> small, large;               // by the size of the bounding box: planes in LDS / in global memory
+    size_t wtotal = 0;
+    for (int k = 0; k < n1; ++k) {
+        const int* o = oi.data() + (size_t)k * EX_OI;
+        if (o[4] < 2 * minarea) continue;            // two seeds take 2 x minarea pixels: it cannot split
+        if ((int64_t)(o[1] - o[0] + 1) * (o[3] - o[2] + 1) <= DB_CELLS) {
+            small.push_back({k + 1, 0});
+        } else {
+            large.push_back({k + 1, (int)wtotal});
+            wtotal += (size_t)o[4];
+        }
+    }
+    if (!small.empty() || !large.empty()) {
+        db_cand* d_cand = nullptr;
+        ZM_TRY(ctx->get("db_cand", (small.size() + large.size()) * sizeof(db_cand), (void**)&d_cand));
+        db_planes w = {};
+        if (!small.empty()) {
+            ZM_HIP(hipMemcpyAsync(d_cand, small.data(), small.size() * sizeof(db_cand), hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_db_tree<true>, dim3((unsigned)small.size()), dim3(256), 0, ctx->stream, d_seg1, b->filt, sigma,
+                               nx, ny, params->detect_thresh, d_obj1, d_cand, N, nroots, deblend->mincont, minarea, w, b->label,
+                               d_split, b->small);
+        }
+        if (!large.empty()) {
+            char* d_p = nullptr;
+            int* d_work = nullptr;
+            db_cand* d_large = d_cand + small.size();
+            ZM_TRY(ctx->get("db_planes", (size_t)np * (6 * 4 + 8 + 1) + 64, (void**)&d_p));
+            ZM_TRY(ctx->get("db_work", wtotal * 3 * 4, (void**)&d_work));
+            w.rq = (unsigned long long*)d_p;
+            w.parent = (int*)(w.rq + np);
+            w.old = w.parent + np; w.seed = w.old + np; w.rn = w.seed + np; w.acc = w.rn + np; w.cst = w.acc + np;
+            w.level = (unsigned char*)(w.cst + np);
+            w.wa = d_work; w.wb = d_work + wtotal; w.wl = d_work + 2 * wtotal;
+            ZM_HIP(hipMemcpyAsync(d_large, large.data(), large.size() * sizeof(db_cand), hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_db_tree<false>, dim3((unsigned)large.size()), dim3(256), 0, ctx->stream, d_seg1, b->filt, sigma,
+                               nx, ny, params->detect_thresh, d_obj1, d_large, N, nroots, deblend->mincont, minarea, w,
+                               b->label, d_split, b->small);
+        }
+        ZM_HIP(hipGetLastError());
+    }
+    ZM_TRY(zm_ex_recount(ctx, b->label, b));
+    zm_ex_count_roots(ctx, b->label, minarea, b);
+    *out_seg1 = d_seg1;
+    *out_split = d_split;
+    return 0;
+}
+
+// PARENT_NUMBER and FLAGS bit 2 of rows 0 .. n - 1 (k_db_parent)
+int zm_db_parent(zm_ctx* ctx, const int* d_obj, int n, const int* d_seg1, const int* d_split, zm_object* out_rows,
+                 int32_t* out_parent) {
+    int* d_par = nullptr;
+    ZM_TRY(ctx->get("db_par", (size_t)n * 2 * 4, (void**)&d_par));
+    hipLaunchKernelGGL(k_db_parent, dim3(zm_div_up(n, 256)), dim3(256), 0, ctx->stream, d_obj, n, d_seg1, d_split, d_par);
+    ZM_HIP(hipGetLastError());
+    std::vector<int> par((size_t)n * 2);
+    ZM_HIP(hipMemcpyAsync(par.data(), d_par, par.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZM_HIP(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; ++k) {
+        if (par[n + k]) out_rows[k].flags |= 2;          // a sub-object of a split parent
+        if (out_parent) out_parent[k] = par[k];
+    }
+    return 0;
+}
+
+int zm_db_check(const zm_deblend_params* deblend) {
+    ZM_CHECK(deblend, "zm_extract_deblend: null deblending parameters");
+    const int N = deblend->nthresh;
+    ZM_CHECK(N >= 2 && N <= DB_MAXN && (N & (N - 1)) == 0 && deblend->mincont >= 0.0 && deblend->mincont <= 1.0,
+             "zm_extract_deblend: bad parameters (nthresh %d: a power of two in 2 .. 64; mincont %g: in [0, 1])", N,
+             deblend->mincont);
+    return 0;
+}
+
 extern "C" int zm_extract_deblend_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
                                       const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
                                       const zm_extract_params* params, int max_objects, zm_object* out_rows,
                                       int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
                                       int* out_status, const zm_deblend_params* deblend, int32_t* out_parent) {
     ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
-    ZM_CHECK(deblend, "zm_extract_deblend: null deblending parameters");
-    const int N = deblend->nthresh;
-    ZM_CHECK(N >= 2 && N <= DB_MAXN && (N & (N - 1)) == 0 && deblend->mincont >= 0.0 && deblend->mincont <= 1.0,
-             "zm_extract_deblend: bad parameters (nthresh %d: a power of two in 2 .. 64; mincont %g: in [0, 1])", N,
-             deblend->mincont);
-    int nroots = 0;
-    while ((1 << nroots) < N) ++nroots;
+    ZM_TRY(zm_db_check(deblend));
     ZM_HIP(hipSetDevice(ctx->device));
     const int np = nx * ny;
     const int cap = max_objects;
@@ -382,60 +467,8 @@ extern "C" int zm_extract_deblend_dev(zm_ctx* ctx, const float* img, const float
     *out_nwritten = 0;
     ZM_CHECK(head[0] == 0, "zm_extract_deblend: a label chain passed its bound of %d steps (status %d)", np, head[0]);
     const int n1 = head[1];
-    int *d_seg1 = nullptr, *d_obj1 = nullptr, *d_split = nullptr;
-    if (n1 > 0) {
-        // the first pass in full: its map and its table, every object of it
-        ZM_TRY(ctx->get("db_seg1", (size_t)np * 4, (void**)&d_seg1));
-        ZM_TRY(ctx->get("db_obj1", (size_t)(n1 + 1) * EX_OI * 4, (void**)&d_obj1));
-        ZM_TRY(ctx->get("db_split", (size_t)n1 * 4, (void**)&d_split));
-        zm_ex_number(ctx, b.label, img, flag, nx, ny, params, n1, d_seg1, d_obj1, &b);
-        ZM_HIP(hipMemsetAsync(d_split, 0, (size_t)n1 * 4, ctx->stream));
-        std::vector<int> oi((size_t)n1 * EX_OI);
-        ZM_HIP(hipMemcpyAsync(oi.data(), d_obj1, oi.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ZM_HIP(hipStreamSynchronize(ctx->stream));
-        std::vector<db_cand> small, large;               // by the size of the bounding box: planes in LDS / in global memory
-        size_t wtotal = 0;
-        for (int k = 0; k < n1; ++k) {
-            const int* o = oi.data() + (size_t)k * EX_OI;
-            if (o[4] < 2 * minarea) continue;            // two seeds take 2 x minarea pixels: it cannot split
-            if ((int64_t)(o[1] - o[0] + 1) * (o[3] - o[2] + 1) <= DB_CELLS) {
-                small.push_back({k + 1, 0});
-            } else {
-                large.push_back({k + 1, (int)wtotal});
-                wtotal += (size_t)o[4];
-            }
-        }
-        if (!small.empty() || !large.empty()) {
-            db_cand* d_cand = nullptr;
-            ZM_TRY(ctx->get("db_cand", (small.size() + large.size()) * sizeof(db_cand), (void**)&d_cand));
-            db_planes w = {};
-            if (!small.empty()) {
-                ZM_HIP(hipMemcpyAsync(d_cand, small.data(), small.size() * sizeof(db_cand), hipMemcpyHostToDevice, ctx->stream));
-                hipLaunchKernelGGL(k_db_tree<true>, dim3((unsigned)small.size()), dim3(256), 0, ctx->stream, d_seg1, b.filt, sigma,
-                                   nx, ny, params->detect_thresh, d_obj1, d_cand, N, nroots, deblend->mincont, minarea, w, b.label,
-                                   d_split, b.small);
-            }
-            if (!large.empty()) {
-                char* d_p = nullptr;
-                int* d_work = nullptr;
-                db_cand* d_large = d_cand + small.size();
-                ZM_TRY(ctx->get("db_planes", (size_t)np * (6 * 4 + 8 + 1) + 64, (void**)&d_p));
-                ZM_TRY(ctx->get("db_work", wtotal * 3 * 4, (void**)&d_work));
-                w.rq = (unsigned long long*)d_p;
-                w.parent = (int*)(w.rq + np);
-                w.old = w.parent + np; w.seed = w.old + np; w.rn = w.seed + np; w.acc = w.rn + np; w.cst = w.acc + np;
-                w.level = (unsigned char*)(w.cst + np);
-                w.wa = d_work; w.wb = d_work + wtotal; w.wl = d_work + 2 * wtotal;
-                ZM_HIP(hipMemcpyAsync(d_large, large.data(), large.size() * sizeof(db_cand), hipMemcpyHostToDevice, ctx->stream));
-                hipLaunchKernelGGL(k_db_tree<false>, dim3((unsigned)large.size()), dim3(256), 0, ctx->stream, d_seg1, b.filt, sigma,
-                                   nx, ny, params->detect_thresh, d_obj1, d_large, N, nroots, deblend->mincont, minarea, w,
-                                   b.label, d_split, b.small);
-            }
-            ZM_HIP(hipGetLastError());
-        }
-        ZM_TRY(zm_ex_recount(ctx, b.label, &b));
-        zm_ex_count_roots(ctx, b.label, minarea, &b);
-    }
+    int *d_seg1 = nullptr, *d_split = nullptr;
+    if (n1 > 0) ZM_TRY(zm_db_split(ctx, img, sigma, flag, nx, ny, params, deblend, n1, &b, &d_seg1, &d_split));
     int* d_obj = nullptr;
     ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
     zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
@@ -449,18 +482,7 @@ extern "C" int zm_extract_deblend_dev(zm_ctx* ctx, const float* img, const float
     *out_nwritten = n;
     if (n == 0) return 0;
     ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows));
-    int* d_par = nullptr;
-    ZM_TRY(ctx->get("db_par", (size_t)n * 2 * 4, (void**)&d_par));
-    hipLaunchKernelGGL(k_db_parent, dim3(zm_div_up(n, 256)), dim3(256), 0, ctx->stream, d_obj, n, d_seg1, d_split, d_par);
-    ZM_HIP(hipGetLastError());
-    std::vector<int> par((size_t)n * 2);
-    ZM_HIP(hipMemcpyAsync(par.data(), d_par, par.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < n; ++k) {
-        if (par[n + k]) out_rows[k].flags |= 2;          // a sub-object of a split parent
-        if (out_parent) out_parent[k] = par[k];
-    }
-    return 0;
+    return zm_db_parent(ctx, d_obj, n, d_seg1, d_split, out_rows, out_parent);
 }
 
 extern "C" int zm_extract_deblend(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,

@@ -702,11 +702,11 @@ extern "C" int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma,
     return zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows);
 }
 
-// host planes in, host planes out, for zm_extract (deblend == nullptr) and zm_extract_deblend
+// host planes in, host planes out, for zm_extract (deblend == nullptr), zm_extract_deblend and zm_extract_clean (clean set)
 int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* flag, int nx, int ny,
                const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows, int32_t* out_segm,
                float* out_filtered, int* out_nwritten, int* out_nfound, int* out_status, const zm_deblend_params* deblend,
-               int32_t* out_parent) {
+               int32_t* out_parent, const zm_clean_params* clean, int32_t* out_nmerged) {
     ZM_CHECK(ctx && img && sigma, "zm_extract: null argument");
     // rows go on gridDim.y, four per workgroup of the filter: 65535 x 4 rows at the most
     ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30 && ny <= 65535 * 4,
@@ -731,7 +731,10 @@ int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
     ZM_TRY(ctx->get("ex_seg", np * 4, (void**)&d_seg));
     ZM_TRY(ctx->get("ex_filt", np * 4, (void**)&d_filt));
     int st = 0;
-    const int rc = deblend ? zm_extract_deblend_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows,
+    const int rc = clean   ? zm_extract_clean_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows,
+                                                  d_seg, d_filt, out_nwritten, out_nfound, &st, deblend, clean, out_parent,
+                                                  out_nmerged)
+                   : deblend ? zm_extract_deblend_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows,
                                                     d_seg, d_filt, out_nwritten, out_nfound, &st, deblend, out_parent)
                            : zm_extract_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows, d_seg,
                                             d_filt, out_nwritten, out_nfound, &st);

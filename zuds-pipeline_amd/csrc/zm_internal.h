@@ -104,6 +104,7 @@ struct zm_ctx {
     // for it and runs beside the small kernels that follow the statistics instead of beside the statistics themselves
     hipEvent_t bk_stats_event = nullptr;
     bool bk_stats_event_valid = false;
+    int cl_npre = 0;                           // objects before CLEAN of the last zm_extract_clean call (slot "cl_stats")
     hipEvent_t lc_tab_event = nullptr;         // behind the last copy out of the pinned image table of lightcurve.hip
     bool timing = false;
     std::string timing_only;                   // non-empty: only this scope is timed
@@ -265,4 +266,11 @@ int zm_ex_rows(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny
 int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* flag, int nx, int ny,
                const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows, int32_t* out_segm,
                float* out_filtered, int* out_nwritten, int* out_nfound, int* out_status, const zm_deblend_params* deblend,
-               int32_t* out_parent);
+               int32_t* out_parent, const zm_clean_params* clean = nullptr, int32_t* out_nmerged = nullptr);
+// the stages of zm_extract_deblend_dev (deblend.hip), which zm_extract_clean_dev (clean.hip) reuses
+int zm_db_check(const zm_deblend_params* deblend);
+int zm_db_split(zm_ctx* ctx, const float* img, const float* sigma, const int32_t* flag, int nx, int ny,
+                const zm_extract_params* params, const zm_deblend_params* deblend, int n1, const zm_ex_bufs* b, int** out_seg1,
+                int** out_split);
+int zm_db_parent(zm_ctx* ctx, const int* d_obj, int n, const int* d_seg1, const int* d_split, zm_object* out_rows,
+                 int32_t* out_parent);

@@ -5,6 +5,11 @@ the operator is stated in DESIGN.md ("Source extraction").  ``Engine.extract`` t
 ``Engine.extract_dev`` device planes (a ``DeviceSubtraction``'s resident difference, noise and mask planes); both are
 attached to ``Engine`` when ``engine.py`` is imported (its last line imports this module).  Like every call on an engine,
 they use the context's one stream and scratch buffers: one call at a time per engine.
+
+Two steps of ``sextractor.conf`` are opt-in keywords of both calls: ``deblend=True | dict(nthresh=, mincont=)``
+(multi-threshold deblending; the table gains PARENT_NUMBER) and ``clean=True | dict(param=)`` (the CLEAN pass on the
+objects of the pass before; the table gains NMERGED).  ``Engine.clean_decide`` is CLEAN's decision alone on a table,
+``Engine.clean_stats`` the per-object sums of the last ``clean=`` call.
 """
 import ctypes as C
 import threading
@@ -16,7 +21,7 @@ from ._lib import as_f32, as_i32, check, ptr, wcs_struct
 from .engine import Engine
 
 __all__ = ['CATALOG_COLUMNS', 'PARAM_COLUMNS', 'extract_params', 'measure_params', 'deblend_params', 'deblend_settings',
-           'TooManyDetectionsError']
+           'clean_params', 'clean_settings', 'TooManyDetectionsError']
 
 # column of the catalog <- field of zm_object (include/zudsmi.h); columns that are not computed are absent
 CATALOG_COLUMNS = [('NUMBER', 'number', 'i4'), ('X_IMAGE', 'x_image', 'f8'), ('Y_IMAGE', 'y_image', 'f8'),
@@ -105,13 +110,50 @@ def deblend_params(deblend=True):
     return p
 
 
-def with_parent(tab, parent):
-    """``tab`` with a PARENT_NUMBER column (int32: the first-pass NUMBER of the object a row was part of)."""
-    out = np.zeros(len(tab), dtype=np.dtype(tab.dtype.descr + [('PARENT_NUMBER', 'i4')]))
+CLEAN_DEFAULTS = dict(param=1.0)                        # CLEAN_PARAM of sextractor.conf
+
+
+def clean_settings(clean=True):
+    """``None`` (no CLEAN pass) or dict(param=) from ``clean=False | True | dict(param=)``.  ``param`` must be finite and
+    lie in [0.1, 10]; anything else raises ValueError."""
+    if clean is None or clean is False:
+        return None
+    kw = {} if clean is True else dict(clean)
+    unknown = set(kw) - set(CLEAN_DEFAULTS)
+    if unknown:
+        raise ValueError(f'clean: unknown keys {sorted(unknown)} (param)')
+    try:
+        param = float(kw.get('param', CLEAN_DEFAULTS['param']))
+    except (TypeError, ValueError):
+        raise ValueError(f'clean: param={kw.get("param")!r} must be a number in [0.1, 10]') from None
+    if not (np.isfinite(param) and 0.1 <= param <= 10.0):
+        raise ValueError(f'clean: param={param!r} must be finite and lie in [0.1, 10]')
+    return dict(param=param)
+
+
+def clean_params(clean=True):
+    """``None`` or the zm_clean_params of ``clean_settings(clean)``."""
+    kw = clean_settings(clean)
+    if kw is None:
+        return None
+    p = _lib.zm_clean_params()
+    _lib.lib().zm_clean_params_default(C.byref(p))
+    p.param = kw['param']
+    return p
+
+
+def with_column(tab, name, values):
+    """``tab`` with one more int32 column."""
+    out = np.zeros(len(tab), dtype=np.dtype(tab.dtype.descr + [(name, 'i4')]))
     for c in tab.dtype.names:
         out[c] = tab[c]
-    out['PARENT_NUMBER'] = parent[:len(tab)]
+    out[name] = values[:len(tab)]
     return out.view(np.recarray)
+
+
+def with_parent(tab, parent):
+    """``tab`` with a PARENT_NUMBER column (int32: the first-pass NUMBER of the object a row was part of)."""
+    return with_column(tab, 'PARENT_NUMBER', parent)
 
 
 def _split_params(columns, params):
@@ -156,7 +198,7 @@ def rows_to_table(rows, n):
     return tab.view(np.recarray)
 
 
-def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, segm, filtered, deblend=None):
+def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, segm, filtered, deblend=None, clean=None):
     # the row array is kept between calls (12 MB at the default capacity: allocating and clearing it takes longer than
     # the extraction of a frame), one per calling thread: threads that share an engine do not share rows
     nrows = max(int(max_objects), 1)
@@ -166,6 +208,16 @@ def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_object
         rows = cache[threading.get_ident()] = (_lib.zm_object * nrows)()
     nw, nf, st = C.c_int(), C.c_int(), C.c_int()
     w = wcs_struct(wcs) if wcs is not None else None
+    if clean is not None:
+        # fn is the CLEAN form of the entry point: PARENT_NUMBER only with deblending, NMERGED always
+        parent, nmerged = np.zeros(nrows, np.int32), np.zeros(nrows, np.int32)
+        check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
+                 int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st),
+                 C.byref(deblend) if deblend is not None else None, C.byref(clean), ptr(parent), ptr(nmerged)), what)
+        tab = rows_to_table(rows, nw.value)
+        if deblend is not None:
+            tab = with_parent(tab, parent)
+        return with_column(tab, 'NMERGED', nmerged), nf.value, st.value
     if deblend is None:
         check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
                  int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st)), what)
@@ -179,7 +231,7 @@ def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_object
 
 
 def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects=MAX_OBJECTS, full=False,
-                    columns='isophotal', deblend=False, **params):
+                    columns='isophotal', deblend=False, clean=False, **params):
     """Object table (numpy record array, columns ``CATALOG_COLUMNS``) and segmentation map (int32, 0 = sky) of ``img``
     (background already subtracted) with per-pixel noise ``sigma``, bad-pixel map ``bad`` and flag plane ``flag``.
 
@@ -193,9 +245,16 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
 
     ``deblend=True`` or ``dict(nthresh=, mincont=)``: multi-threshold deblending (``zm_extract_deblend``; DESIGN.md,
     "Deblending").  Objects are numbered after the split, sub-objects of a split parent carry FLAGS bit 2, and the table
-    gains the column PARENT_NUMBER.  Where nothing splits, table and map are those of the default call."""
+    gains the column PARENT_NUMBER.  Where nothing splits, table and map are those of the default call.
+
+    ``clean=True`` or ``dict(param=)``: the CLEAN pass (``zm_extract_clean``; DESIGN.md, "CLEAN") on the objects of the
+    pass before, deblended or not: an object whose neighbour's wing explains it is folded into that neighbour, the merged
+    objects are renumbered and measured on the union of their pixels, and the table gains the column NMERGED (objects
+    from before CLEAN in the row; 1 = untouched).  Where nothing is absorbed, table and map are those of the same call
+    without ``clean``."""
     params, mp = _split_params(columns, params)
     db = deblend_params(deblend)
+    cl = clean_params(clean)
     img, sigma, flag = as_f32(img), as_f32(sigma), as_i32(flag)
     ny, nx = img.shape
     if sigma.shape != img.shape:
@@ -208,9 +267,10 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     p = extract_params(**params)
     segm = np.empty((ny, nx), np.int32)
     filt = np.empty((ny, nx), np.float32) if full else None
-    fn, what = (self.L.zm_extract, 'zm_extract') if db is None else (self.L.zm_extract_deblend, 'zm_extract_deblend')
+    fn, what = ((self.L.zm_extract_clean, 'zm_extract_clean') if cl is not None else
+                (self.L.zm_extract, 'zm_extract') if db is None else (self.L.zm_extract_deblend, 'zm_extract_deblend'))
     tab, nfound, status = _call(self, fn, what, ptr(img), ptr(sigma), ptr(bad), ptr(flag), nx, ny,
-                                wcs, p, max_objects, ptr(segm), ptr(filt), db)
+                                wcs, p, max_objects, ptr(segm), ptr(filt), db, cl)
     ext = None
     if mp is not None:
         first = tab
@@ -218,6 +278,8 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
                             ptr(segm), nx, ny, wcs, mp, len(tab))
         if db is not None:
             tab = with_parent(tab, first['PARENT_NUMBER'])
+        if cl is not None:
+            tab = with_column(tab, 'NMERGED', first['NMERGED'])
     if full and ext is not None:
         return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext)
     if full:
@@ -226,32 +288,68 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
 
 
 def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objects=MAX_OBJECTS, segm=None,
-                        columns='isophotal', deblend=False, **params):
+                        columns='isophotal', deblend=False, clean=False, **params):
     """The same on device planes (addresses: float32 img, sigma; uint8 bad or None; int32 flag or None; ``segm``: an
     int32 device plane that takes the segmentation map, or None).  Returns (table, number found).
     ``columns='param'`` needs the segmentation map for its second pass: without ``segm`` a plane is allocated for the
-    call.  ``deblend``: as for ``Engine.extract``."""
+    call.  ``deblend``, ``clean``: as for ``Engine.extract``."""
     params, mp = _split_params(columns, params)
     db = deblend_params(deblend)
+    cl = clean_params(clean)
     own = None
     if mp is not None and not segm:
         from . import hipmem
         own = hipmem.DeviceBuffer(int(nx) * int(ny) * 4)         # (freed when this call returns)
         segm = own.ptr
     p = extract_params(**params)
-    fn, what = ((self.L.zm_extract_dev, 'zm_extract_dev') if db is None else
+    fn, what = ((self.L.zm_extract_clean_dev, 'zm_extract_clean_dev') if cl is not None else
+                (self.L.zm_extract_dev, 'zm_extract_dev') if db is None else
                 (self.L.zm_extract_deblend_dev, 'zm_extract_deblend_dev'))
     tab, nfound, _ = _call(self, fn, what, int(img), int(sigma), int(bad) if bad else None,
                            int(flag) if flag else None, int(nx), int(ny), wcs, p, max_objects,
-                           int(segm) if segm else None, None, db)
+                           int(segm) if segm else None, None, db, cl)
     if mp is not None:
         first = tab
         tab, _ = _measure(self, self.L.zm_extract_measure_dev, 'zm_extract_measure_dev', int(img), int(sigma),
                           int(bad) if bad else None, int(segm), int(nx), int(ny), wcs, mp, len(tab))
         if db is not None:
             tab = with_parent(tab, first['PARENT_NUMBER'])
+        if cl is not None:
+            tab = with_column(tab, 'NMERGED', first['NMERGED'])
     return tab, nfound
 
 
+def _engine_clean_stats(self):
+    """(F, T, m) of every object from before CLEAN of this engine's last ``clean=`` call (``zm_extract_clean_stats``):
+    float64 sum of the filtered values, float32 threshold at the peak pixel, float32 DETECT_MINAREA-th largest excess over
+    the local threshold."""
+    n = C.c_int()
+    check(self.L.zm_extract_clean_stats(self._ctx, 0, None, None, None, C.byref(n)), 'zm_extract_clean_stats')
+    F, T, m = np.zeros(n.value, np.float64), np.zeros(n.value, np.float32), np.zeros(n.value, np.float32)
+    if n.value:
+        check(self.L.zm_extract_clean_stats(self._ctx, n.value, ptr(F), ptr(T), ptr(m), C.byref(n)), 'zm_extract_clean_stats')
+    return F, T, m
+
+
+def _engine_clean_decide(self, rows, fdflux, dthresh, mthresh, minarea=5, clean=True):
+    """(into, root) of ``zm_clean_decide``: the CLEAN decision alone on a table.  ``rows``: a numpy array of dtype
+    ``np.dtype(_lib.zm_object)`` (number = index + 1); the NUMBER of the absorber of every object (0: none) and the NUMBER at
+    the end of its chain."""
+    rows = np.ascontiguousarray(rows, np.dtype(_lib.zm_object))
+    n = len(rows)
+    F, T, m = (np.ascontiguousarray(a, dt) for a, dt in ((fdflux, np.float64), (dthresh, np.float32), (mthresh, np.float32)))
+    if not len(F) == len(T) == len(m) == n:
+        raise ValueError('clean_decide: rows, fdflux, dthresh and mthresh differ in length')
+    cl = clean_params(clean)
+    if cl is None:
+        raise ValueError('clean_decide: clean must be True or dict(param=)')
+    into, root = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    check(self.L.zm_clean_decide(self._ctx, n, ptr(rows), ptr(F), ptr(T), ptr(m), int(minarea), C.byref(cl), ptr(into),
+                                 ptr(root)), 'zm_clean_decide')
+    return into, root
+
+
 Engine.extract = _engine_extract
+Engine.clean_stats = _engine_clean_stats
+Engine.clean_decide = _engine_clean_decide
 Engine.extract_dev = _engine_extract_dev

@@ -57,10 +57,12 @@ class SubtractionJob(object):
     the network and the ML cut at ``rb_cut`` or ``RB_CUT[fid]``; ``max_detections`` and ``stamps`` then see the rows that
     survive that cut, as the reference's driver does.
     ``deblend`` (with ``detect``): False, True or dict(nthresh=, mincont=), the multi-threshold deblending of
-    ``DeviceSubtraction.candidates``; the result then carries ``deblend``, the settings used."""
+    ``DeviceSubtraction.candidates``; the result then carries ``deblend``, the settings used.
+    ``clean`` (with ``detect``): False, True or dict(param=), the CLEAN pass of ``DeviceSubtraction.candidates``; the
+    result then carries ``clean``, the settings used."""
 
     def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
-                 max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False):
+                 max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False, clean=False):
         if stamps and not detect:
             raise ValueError('stamps needs detect')
         if rb_model is not None:
@@ -70,8 +72,11 @@ class SubtractionJob(object):
             rb_cut_for(fid, rb_cut)                      # (raises when neither names a cut)
         if deblend and not detect:
             raise ValueError('deblend needs detect')
-        from .extract import deblend_settings
+        if clean and not detect:
+            raise ValueError('clean needs detect')
+        from .extract import clean_settings, deblend_settings
         self.deblend = deblend_settings(deblend)         # (raises on settings the extractor refuses)
+        self.clean = clean_settings(clean)
         self.rb_model, self.fid, self.rb_cut = rb_model, fid, rb_cut
         self.sci, self.ref, self.radec = sci, ref, radec
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag
@@ -179,6 +184,8 @@ def _detect(ch, job, out):
         dbkw = {}
         if getattr(job, 'deblend', None):
             dbkw['deblend'] = out['deblend'] = job.deblend
+        if getattr(job, 'clean', None):
+            dbkw['clean'] = out['clean'] = job.clean
         cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'], **rbkw, **dbkw)
     except _lib.ZMError as exc:
         out['cat'], out['detect_error'] = None, str(exc)

@@ -7,11 +7,13 @@ extraction work): that is what the coadd / subtraction path asks for.  ``catalog
 runs the extractor with the operator of ``sextractor.conf`` as DESIGN.md ("Source extraction") states it:
 filter ``default.conv``, ``DETECT_THRESH`` 1.5, ``DETECT_MINAREA`` 5, no deblending, no cleaning.  ``deblend=True`` (or
 ``dict(nthresh=, mincont=)``) opts into the multi-threshold deblending of DESIGN.md ("Deblending"); only then may
-``sextractor_kws`` carry ``DEBLEND_NTHRESH`` and ``DEBLEND_MINCONT``.
+``sextractor_kws`` carry ``DEBLEND_NTHRESH`` and ``DEBLEND_MINCONT``.  ``clean=True`` (or ``dict(param=)``) opts into the
+CLEAN pass of DESIGN.md ("CLEAN"); only then may ``sextractor_kws`` carry ``CLEAN`` (which must say yes) and
+``CLEAN_PARAM``.
 
 ``sextractor_kws``: ``DETECT_THRESH``, ``DETECT_MINAREA``, ``FILTER``, ``PHOT_APERTURES`` (one diameter),
 ``SATUR_LEVEL``, ``BACK_SIZE``, ``BACK_FILTERSIZE`` are honoured; keys that would change something this version does
-not do (``DEBLEND_*`` without ``deblend=True``, ``CLEAN*``, ``MASK_TYPE``, ``FILTER_NAME``, a ``WEIGHT_TYPE`` other than
+not do (``DEBLEND_*`` without ``deblend=True``, ``CLEAN*`` without ``clean=True``, ``MASK_TYPE``, ``FILTER_NAME``, a ``WEIGHT_TYPE`` other than
 ``MAP_WEIGHT``, an ``ANALYSIS_THRESH`` different from ``DETECT_THRESH``) raise ``ValueError``; bookkeeping keys are ignored.
 ``columns='param'`` asks for the wide table (``extract.PARAM_COLUMNS``: every column of ``sextractor.param``); only then
 may ``sextractor_kws`` carry ``PHOT_AUTOPARAMS`` (two values).
@@ -48,22 +50,31 @@ def _yes(v):
 _DEBLEND_KEYS = {'DEBLEND_NTHRESH': 'nthresh', 'DEBLEND_MINCONT': 'mincont'}
 
 
-def extraction_settings(sextractor_kws=None, header=None, deblend=False):
+def extraction_settings(sextractor_kws=None, header=None, deblend=False, clean=False):
     """Keyword arguments of ``Engine.extract`` from ``sextractor_kws`` and the image header (``SATURATE``).
     ``deblend``: False, True or dict(nthresh=, mincont=); only when it is set are ``DEBLEND_NTHRESH`` and
-    ``DEBLEND_MINCONT`` accepted (they override the dict), and the result then carries ``deblend``."""
-    from .extract import deblend_settings
+    ``DEBLEND_MINCONT`` accepted (they override the dict), and the result then carries ``deblend``.
+    ``clean``: False, True or dict(param=); only when it is set are ``CLEAN`` (which must say yes: the keyword asked for the
+    pass) and ``CLEAN_PARAM`` (which overrides the dict) accepted, and the result then carries ``clean``."""
+    from .extract import clean_settings, deblend_settings
     kws = {str(k).upper(): v for k, v in (sextractor_kws or {}).items()}
     db = deblend_settings(deblend)
     if db is not None:
         for k in [k for k in kws if k in _DEBLEND_KEYS]:
             db[_DEBLEND_KEYS[k]] = kws.pop(k)
         db = deblend_settings(db)
+    cl = clean_settings(clean)
+    if cl is not None:
+        if 'CLEAN' in kws and not _yes(kws.pop('CLEAN')):
+            raise ValueError('sextractor_kws: CLEAN says no, but clean= asks for the pass')
+        if 'CLEAN_PARAM' in kws:
+            cl['param'] = kws.pop('CLEAN_PARAM')
+        cl = clean_settings(cl)
     for k in kws:
         if k in _REFUSED or k.startswith(_REFUSED_PREFIXES):
             raise ValueError(f'sextractor_kws: {k} would change a step this extractor does not have '
-                             f'(deblending needs deblend=True; cleaning, mask correction and other filters are not in '
-                             f'this version)')
+                             f'(deblending needs deblend=True, cleaning clean=True; mask correction and other filters '
+                             f'are not in this version)')
         if k not in _HONOURED and k not in _IGNORED:
             raise ValueError(f'sextractor_kws: unknown key {k}')
     thresh = float(kws.get('DETECT_THRESH', 1.5))
@@ -80,6 +91,8 @@ def extraction_settings(sextractor_kws=None, header=None, deblend=False):
                satur_level=float(satur), aper_radius=float(aper[0]) / 2.0)
     if db is not None:
         out['deblend'] = db
+    if cl is not None:
+        out['clean'] = cl
     return out
 
 
@@ -133,7 +146,7 @@ def measurement_settings(sextractor_kws=None):
     return rest, dict(kron_fact=float(auto[0]), kron_min_radius=float(auto[1]))
 
 
-def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=False):
+def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=False, clean=False):
     """(PipelineFITSCatalog, segmentation map) of the background-subtracted plane ``sub``: noise = the image's
     rms_image, bad = weight 0, flags = the mask."""
     from .catalog import PipelineFITSCatalog
@@ -147,7 +160,7 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
         second = {}
     else:
         raise ValueError(f"columns={columns!r}: 'isophotal' or 'param'")
-    settings = extraction_settings(sextractor_kws, image.header, deblend=deblend)
+    settings = extraction_settings(sextractor_kws, image.header, deblend=deblend, clean=clean)
     settings.update(second)
     mask = getattr(image, 'mask_image', None)
     try:
@@ -161,6 +174,7 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
     cat.basename = os.path.basename(base).replace('.fits', '.cat')
     cat.data = tab
     cat.deblend = settings.get('deblend')
+    cat.clean = settings.get('clean')
     cat.header = dict(image.header or {})
     cat.header_comments = dict(image.header_comments or {})
     if image.ismapped:
@@ -170,12 +184,13 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
 
 
 def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir='/tmp',
-                   use_weightmap=True, sextractor_kws=None, catalog=False, columns='isophotal', deblend=False):
+                   use_weightmap=True, sextractor_kws=None, catalog=False, columns='isophotal', deblend=False,
+                   clean=False):
     """Produce the requested check-images as FITSImage objects, written next to
     the image when it is mapped (``zuds/sextractor.py:110-150``).  The returned
     list starts with the catalog slot: ``None``, or with ``catalog=True`` (or when ``segm`` is among the
     check-images) the ``PipelineFITSCatalog`` of the image; ``columns='param'``: with the wide table; ``deblend``: with
-    multi-threshold deblending (``Engine.extract``)."""
+    multi-threshold deblending, ``clean``: with the CLEAN pass (``Engine.extract``)."""
     from .engine import get_engine
     from .image import FITSImage
     call = prepare_sextractor(image, None, checkimage_type=checkimage_type,
@@ -193,7 +208,7 @@ def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir
     planes = {'bkg': bkg, 'rms': rms, 'bkgsub': sub}
     result = [None]
     if extracting:
-        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws, columns, deblend)
+        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws, columns, deblend, clean)
     for t, name in zip(call['types'], call['outnames']):
         product = FITSImage()
         product.basename = os.path.basename(name)

@@ -29,11 +29,21 @@
 // lim != nullptr (zm_hp_params.limits_dev): the lower limits come from the background estimates that
 // zm_median_mad2_async_dev left on the device - {median, sigma, count} of the science frame, then of the
 // template - with the host's arithmetic (double, then rounded to float as a kernel argument would be)
+// The first kernel of a subtraction also clears the fit's counters and the rounds' flag words (zero0 / zero1: the
+// first workgroup does it): two 5-us fills ahead of the first round are gone from the stream.
+static __device__ __forceinline__ void hp_zero_words(int* __restrict__ zero0, int nzero0, int* __restrict__ zero1, int nzero1) {
+    if (blockIdx.x != 0) return;
+    if (zero0) for (int k = threadIdx.x; k < nzero0; k += blockDim.x) zero0[k] = 0;
+    if (zero1) for (int k = threadIdx.x; k < nzero1; k += blockDim.x) zero1[k] = 0;
+}
 __global__ void k_hp_valid(const float* __restrict__ sci, const float* __restrict__ ref,
                            const uint8_t* __restrict__ bpm, int64_t n, float il, float iu,
                            float tl, float tu, uint8_t* __restrict__ bad,
-                           const double* __restrict__ lim, double nsig) {
+                           const double* __restrict__ lim, double nsig,
+                           int* __restrict__ zero0 = nullptr, int nzero0 = 0,
+                           int* __restrict__ zero1 = nullptr, int nzero1 = 0) {
     int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    hp_zero_words(zero0, nzero0, zero1, nzero1);
     if (lim) {
         il = (float)(lim[0] - nsig * lim[1]);
         tl = (float)(lim[3] - nsig * lim[4]);
@@ -88,8 +98,11 @@ __global__ __launch_bounds__(256) void k_hp_valid_rows(const float* __restrict__
                                                        const uint8_t* __restrict__ bpm, int nx, int ny, float il, float iu,
                                                        float tl, float tu, const double* __restrict__ lim, double nsig,
                                                        int hw1, int hw2, uint8_t* __restrict__ bad,
-                                                       uint8_t* __restrict__ out1, uint8_t* __restrict__ out2) {
+                                                       uint8_t* __restrict__ out1, uint8_t* __restrict__ out2,
+                                                       int* __restrict__ zero0 = nullptr, int nzero0 = 0,
+                                                       int* __restrict__ zero1 = nullptr, int nzero1 = 0) {
     extern __shared__ int ra_pre[];                       // [nx + 1], ra_pre[0] = 0
+    hp_zero_words(zero0, nzero0, zero1, nzero1);
     __shared__ int wsum[HP_ROWMAX / 64], wtot[4];         // bad pixels per (chunk of 256, wave), then their offsets
     if (lim) {
         il = (float)(lim[0] - nsig * lim[1]);
@@ -629,27 +642,40 @@ __global__ __launch_bounds__(256) void k_hp_build(const hp_plan P, const double*
 }
 
 #define BB_CH 128
+#define HBB_PAIRS 5   // pairs of source vectors per workgroup of k_hp_build_blk
+#define BU_CH 32      // changed cells per staging step of the later rounds' update
+#define BB_LDS (BB_CH * 18 + BB_CH / 2)                  // doubles of LDS either form of k_hp_build_blk carves up
+// pair index -> (n1, n2 <= n1) (a triangular grid: the square grid dispatched as many empty workgroups again)
+static __device__ __forceinline__ void hp_pair_decode(const int pair, int* n1o, int* n2o) {
+    int n1 = (int)((sqrtf(8.f * (float)pair + 1.f) - 1.f) * 0.5f);
+    while (n1 * (n1 + 1) / 2 > pair) --n1;
+    while ((n1 + 1) * (n1 + 2) / 2 <= pair) ++n1;
+    *n1o = n1;
+    *n2o = pair - n1 * (n1 + 1) / 2;
+}
+// What one cell adds to an entry of the normal matrix and of the right-hand side (the ONE place where the block forms
+// do that arithmetic: the full build and the later rounds' update call it, so that what a cell put in is what it takes
+// out, in the same products and roundings).  w1, w2: the spatial terms of the two unknowns (1 where a source vector
+// carries none), g, gr: the cell's Gram entry of the pair of source vectors and its right-hand-side entry.
+static __device__ __forceinline__ void hp_blk_entry_add(const double w1, const double w2, const double g, const double gr,
+                                                     const bool do_rhs, double& acc, double& racc) {
+    acc += w1 * w2 * g;
+    if (do_rhs) racc += w1 * gr;
+}
 // The same sums by blocks of source-vector pairs: workgroup (n1, n2 <= n1) of a region owns the
 // nkp x nkp unknowns (n1, p1) x (n2, p2); per cell it needs ONE Gram entry G[n1][n2] (a uniform,
 // scalar load) and the spatial terms of its threads, i.e. 2 loads and 3 flops per unknown pair and
 // cell where k_hp_build decodes and gathers per pair (1.2 x 10^8 pair-cell products per round-1
 // build).  Same products, same cell order: the results are identical to the last bit.
+// (the full build - sign 0 of k_hp_build - from every active cell of the region; sh: BB_LDS doubles of LDS)
 static __device__ __forceinline__ void hp_build_blk_body(const int reg, const int pair, const hp_plan& P, const double* __restrict__ G,
                                                       const double* __restrict__ phi,
                                                       const int* __restrict__ active,
-                                                      const int* __restrict__ chg, int sign,
                                                       double* __restrict__ A,
-                                                      double* __restrict__ rhs, const int* __restrict__ guard,
-                                                      unsigned* __restrict__ zero, int nzero,
-                                                      const double* __restrict__ Gold,
-                                                      const double* __restrict__ phiold,
-                                                      const int* __restrict__ need) {
-    if (guard && *guard == 0) return;
-    // (a triangular grid: x = pair index of (n1, n2 <= n1) - the square grid dispatched as many empty workgroups again)
-    int n1 = (int)((sqrtf(8.f * (float)pair + 1.f) - 1.f) * 0.5f);
-    while (n1 * (n1 + 1) / 2 > pair) --n1;
-    while ((n1 + 1) * (n1 + 2) / 2 <= pair) ++n1;
-    const int n2 = pair - n1 * (n1 + 1) / 2;
+                                                      double* __restrict__ rhs,
+                                                      unsigned* __restrict__ zero, int nzero, double* sh) {
+    int n1, n2;
+    hp_pair_decode(pair, &n1, &n2);
     if (zero && n1 == 0 && n2 == 0)                      // (the hand-over words of this round's k_chol_df)
         for (int k = threadIdx.x; k < nzero; k += 256) zero[(size_t)reg * nzero + k] = 0u;
     const int p1 = threadIdx.x >> 4, p2 = threadIdx.x & 15;
@@ -659,72 +685,181 @@ static __device__ __forceinline__ void hp_build_blk_body(const int reg, const in
     const int c2 = n2 == 0 ? 0 : (k2 ? 1 + (n2 - 1) * P.nkp + p2 : 1 + nk + (n2 - P.nc));
     const bool live = p1 < (k1 ? P.nkp : 1) && p2 < (k2 ? P.nkp : 1) && c2 <= c1;
     const bool do_rhs = (c2 == 0);
-    const int* list = chg + P.ncell + reg * (P.ncellr + 1);
-    const int ncand = (sign == 0) ? P.ncellr : list[0];
     // the candidates' Gram entries, right-hand-side entries, spatial terms and flags are staged in
     // LDS, BB_CH cells at a time (one memory latency per chunk); the sums then run out of LDS
-    __shared__ double gs[BB_CH], grs[BB_CH], phs[BB_CH * 16];
-    __shared__ int ons[BB_CH];
+    double *gs = sh, *grs = sh + BB_CH, *phs = sh + 2 * BB_CH;
+    int* ons = reinterpret_cast<int*>(sh + 18 * BB_CH);
     const int tid = threadIdx.x;
     const size_t ia = (size_t)reg * (size_t)(P.nunk + 1) * P.nunk + (size_t)c1 * P.nunk + c2;
-    // sign == 2 (round 4): both updates of a rejection round in one launch - the changed cells leave with the Gram
-    // matrix and spatial terms they had (kept by k_hp_gram_sum / k_hp_vectors when they wrote the new ones: Gold,
-    // phiold; a cell that was dropped still has them in place), then come back with the new ones; an entry takes
-    // the two sums one after the other, as the two launches applied them: the same roundings.
-    double av = 0.0, rv = 0.0;
-    bool touched = false;
-    const int npass = sign == 2 ? 2 : 1;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int sg = sign == 2 ? (pass == 0 ? -1 : 1) : sign;
-        double acc = 0.0, racc = 0.0;
-        bool any = false;
-        for (int s0 = 0; s0 < ncand; s0 += BB_CH) {
-            const int nch = min(BB_CH, ncand - s0);
-            __syncthreads();
-            if (tid < nch) {
-                const int cell = (sg == 0) ? reg * P.ncellr + s0 + tid : list[1 + s0 + tid];
-                const int on = !(active[cell] < 0 && sg >= 0);
-                const bool was = sign == 2 && pass == 0 && need[cell];       // recomputed since: the old copy
-                const double* Gc = (was ? Gold : G) + (size_t)cell * HP_MAXX * HP_MAXX;
-                ons[tid] = on;
-                gs[tid] = on ? Gc[n1 * HP_MAXX + n2] : 0.0;
-                grs[tid] = (on && n2 == 0) ? Gc[n1 * HP_MAXX + P.nE] : 0.0;
+    double acc = 0.0, racc = 0.0;
+    for (int s0 = 0; s0 < P.ncellr; s0 += BB_CH) {
+        const int nch = min(BB_CH, P.ncellr - s0);
+        __syncthreads();
+        if (tid < nch) {
+            const int cell = reg * P.ncellr + s0 + tid;
+            const int on = active[cell] >= 0;
+            const double* Gc = G + (size_t)cell * HP_MAXX * HP_MAXX;
+            ons[tid] = on;
+            gs[tid] = on ? Gc[n1 * HP_MAXX + n2] : 0.0;
+            grs[tid] = (on && n2 == 0) ? Gc[n1 * HP_MAXX + P.nE] : 0.0;
+        }
+        for (int e = tid; e < nch * P.nkp; e += 256) {
+            const int k = e / P.nkp, pp = e - k * P.nkp;
+            phs[k * 16 + pp] = phi[(size_t)(reg * P.ncellr + s0 + k) * P.nkp + pp];
+        }
+        __syncthreads();
+        if (live) {
+            for (int k = 0; k < nch; ++k) {
+                if (!ons[k]) continue;
+                const double w1 = k1 ? phs[k * 16 + p1] : 1.0, w2 = k2 ? phs[k * 16 + p2] : 1.0;
+                hp_blk_entry_add(w1, w2, gs[k], do_rhs ? grs[k] : 0.0, do_rhs, acc, racc);
             }
-            for (int e = tid; e < nch * P.nkp; e += 256) {
-                const int k = e / P.nkp, pp = e - k * P.nkp;
-                const int cell = (sg == 0) ? reg * P.ncellr + s0 + k : list[1 + s0 + k];
-                const bool was = sign == 2 && pass == 0 && need[cell];
-                phs[k * 16 + pp] = (was ? phiold : phi)[(size_t)cell * P.nkp + pp];
+        }
+    }
+    if (!live) return;
+    A[ia] = acc;
+    if (do_rhs) rhs[(size_t)reg * P.nunk + c1] = racc;
+}
+
+// The later rounds' update of the retained normal matrix (sign 2 of k_hp_build_blk): the changed cells of the region
+// (chg's list) leave with the Gram matrix and spatial terms they had (kept by k_hp_gram_sum / k_hp_vectors when they
+// wrote the new ones: Gold, phiold, where need[cell] says so; a cell that was dropped still has them in place), then
+// come back with the new ones (cells that still have a substamp); an entry takes the two sums one after the other,
+// as two launches (sign -1, then + 1) would apply them: the same roundings.
+// A workgroup takes its HBB_PAIRS pairs of source vectors TOGETHER: the changed cells' spatial terms (old and new) and
+// flags are staged once, the Gram entries of all its pairs (old and new) and its entries of A go out in the same
+// batch of loads, one barrier, then the sums.  (Before: pair after pair and pass after pass, ten steps of
+// barrier - list -> flags -> Gram entry - barrier - sum, each a chain of dependent loads: 19 - 47 us per round for
+// a handful of cells, all of it latency.)  A list longer than BU_CH cells is staged in chunks, in list order; the
+// leaving and the returning sums of an entry run side by side, each in the order it had.
+static __device__ __forceinline__ void hp_update_blk_body(const int reg, const int pair0, const hp_plan& P, const double* __restrict__ G,
+                                                       const double* __restrict__ phi, const int* __restrict__ active,
+                                                       const int* __restrict__ chg, double* __restrict__ A,
+                                                       double* __restrict__ rhs, unsigned* __restrict__ zero, int nzero,
+                                                       const double* __restrict__ Gold, const double* __restrict__ phiold,
+                                                       const int* __restrict__ need, double* sh) {
+    static_assert(HBB_PAIRS * BU_CH <= 256 && BU_CH * 16 == 512, "one Gram item and two spatial-term items per thread");
+    static_assert(4 * HBB_PAIRS * BU_CH + 2 * BU_CH * 16 + BU_CH <= BB_LDS, "the update's staging fits the build's LDS");
+    // [pass: 0 leaving, 1 returning][pair][cell] Gram / right-hand-side entries, [pass][cell][16] spatial terms, flags
+    double (*ug)[HBB_PAIRS][BU_CH] = reinterpret_cast<double (*)[HBB_PAIRS][BU_CH]>(sh);
+    double (*ugr)[HBB_PAIRS][BU_CH] = reinterpret_cast<double (*)[HBB_PAIRS][BU_CH]>(sh + 2 * HBB_PAIRS * BU_CH);
+    double (*uph)[BU_CH * 16] = reinterpret_cast<double (*)[BU_CH * 16]>(sh + 4 * HBB_PAIRS * BU_CH);
+    int* uon = reinterpret_cast<int*>(sh + 4 * HBB_PAIRS * BU_CH + 2 * BU_CH * 16);     // the cell comes back
+    const int tid = threadIdx.x;
+    const int npair = P.nE * (P.nE + 1) / 2;
+    if (zero && pair0 == 0)                              // (the hand-over words of this round's k_chol_df)
+        for (int k = tid; k < nzero; k += 256) zero[(size_t)reg * nzero + k] = 0u;
+    const int* list = chg + P.ncell + reg * (P.ncellr + 1);
+    const int ncand = list[0];
+    if (ncand <= 0) return;
+    const int p1 = tid >> 4, p2 = tid & 15;
+    const int nk = (P.nc - 1) * P.nkp;
+    // this thread's entry of every pair, and its loads from A / rhs: they fly while the cells are staged
+    bool k1[HBB_PAIRS], k2[HBB_PAIRS], live[HBB_PAIRS], do_rhs[HBB_PAIRS], any1[HBB_PAIRS];
+    size_t ia[HBB_PAIRS], ir[HBB_PAIRS];
+    double av[HBB_PAIRS], rv[HBB_PAIRS], acc0[HBB_PAIRS], racc0[HBB_PAIRS], acc1[HBB_PAIRS], racc1[HBB_PAIRS];
+    {
+        int n1, n2;
+        hp_pair_decode(pair0, &n1, &n2);
+#pragma unroll
+        for (int q = 0; q < HBB_PAIRS; ++q) {
+            k1[q] = n1 >= 1 && n1 < P.nc;
+            k2[q] = n2 >= 1 && n2 < P.nc;
+            const int c1 = n1 == 0 ? 0 : (k1[q] ? 1 + (n1 - 1) * P.nkp + p1 : 1 + nk + (n1 - P.nc));
+            const int c2 = n2 == 0 ? 0 : (k2[q] ? 1 + (n2 - 1) * P.nkp + p2 : 1 + nk + (n2 - P.nc));
+            live[q] = pair0 + q < npair && p1 < (k1[q] ? P.nkp : 1) && p2 < (k2[q] ? P.nkp : 1) && c2 <= c1;
+            do_rhs[q] = (c2 == 0);
+            ia[q] = (size_t)reg * (size_t)(P.nunk + 1) * P.nunk + (size_t)c1 * P.nunk + c2;
+            ir[q] = (size_t)reg * P.nunk + c1;
+            any1[q] = false;
+            av[q] = rv[q] = acc0[q] = racc0[q] = acc1[q] = racc1[q] = 0.0;
+            if (live[q]) {
+                av[q] = A[ia[q]];
+                if (do_rhs[q]) rv[q] = rhs[ir[q]];
             }
-            __syncthreads();
-            if (live) {
-                for (int k = 0; k < nch; ++k) {
-                    if (!ons[k]) continue;
-                    any = true;
-                    const double w1 = k1 ? phs[k * 16 + p1] : 1.0, w2 = k2 ? phs[k * 16 + p2] : 1.0;
-                    acc += w1 * w2 * gs[k];
-                    if (do_rhs) racc += w1 * grs[k];
+            if (++n2 > n1) { ++n1; n2 = 0; }             // the next pair of the triangle
+        }
+    }
+    // what this thread stages: the Gram entries of (pair gq, cell gk), the spatial terms (cell, term) of two slots
+    const int gq = min(tid / BU_CH, HBB_PAIRS - 1), gk = tid % BU_CH;
+    const bool gdo = tid < HBB_PAIRS * BU_CH && pair0 + gq < npair;
+    int gn1, gn2;
+    hp_pair_decode(min(pair0 + gq, npair - 1), &gn1, &gn2);
+    for (int s0 = 0; s0 < ncand; s0 += BU_CH) {
+        const int nch = min(BU_CH, ncand - s0);
+        __syncthreads();
+        {
+            // every address is clamped into its array and every load goes out whether or not its value is kept:
+            // list entries first, everything else in one batch behind them
+            const int cg = list[1 + s0 + min(gk, nch - 1)];
+            int cp[2], pp[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int e = tid + 256 * u;
+                cp[u] = list[1 + s0 + min(e >> 4, nch - 1)];
+                pp[u] = min(e & 15, P.nkp - 1);
+            }
+            const int wasg = need[cg], ong = active[cg] >= 0;
+            const double* Gn = G + (size_t)cg * HP_MAXX * HP_MAXX;
+            const double* Go = Gold + (size_t)cg * HP_MAXX * HP_MAXX;
+            const double gnew = Gn[gn1 * HP_MAXX + gn2], gold = Go[gn1 * HP_MAXX + gn2];
+            const double rnew = Gn[gn1 * HP_MAXX + P.nE], rold = Go[gn1 * HP_MAXX + P.nE];
+            int wasp[2];
+            double fnew[2], fold[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                wasp[u] = need[cp[u]];
+                fnew[u] = phi[(size_t)cp[u] * P.nkp + pp[u]];
+                fold[u] = phiold[(size_t)cp[u] * P.nkp + pp[u]];
+            }
+            if (gdo && gk < nch) {
+                ug[0][gq][gk] = wasg ? gold : gnew;      // (recomputed since: the old copy)
+                ugr[0][gq][gk] = gn2 == 0 ? (wasg ? rold : rnew) : 0.0;
+                ug[1][gq][gk] = ong ? gnew : 0.0;
+                ugr[1][gq][gk] = (ong && gn2 == 0) ? rnew : 0.0;
+                if (gq == 0) uon[gk] = ong;              // (every changed cell leaves, those that still have a substamp come back)
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int e = tid + 256 * u;
+                if ((e >> 4) < nch && (e & 15) < P.nkp) {
+                    uph[0][e] = wasp[u] ? fold[u] : fnew[u];
+                    uph[1][e] = fnew[u];
                 }
             }
         }
-        if (!live) continue;
-        if (sg == 0) {
-            A[ia] = acc;
-            if (do_rhs) rhs[(size_t)reg * P.nunk + c1] = racc;
-        } else if (any) {
-            if (!touched) {
-                av = A[ia];
-                if (do_rhs) rv = rhs[(size_t)reg * P.nunk + c1];
-                touched = true;
-            }
-            av += (double)sg * acc;
-            if (do_rhs) rv += (double)sg * racc;
+        __syncthreads();
+        // cell by cell, in list order; a cell's spatial terms and flag are read once for all the pairs (the sums
+        // run out of LDS: its reads are what they cost)
+        for (int k = 0; k < nch; ++k) {
+            const double f1o = uph[0][k * 16 + p1], f2o = uph[0][k * 16 + p2];
+            const double f1n = uph[1][k * 16 + p1], f2n = uph[1][k * 16 + p2];
+            const bool back = uon[k] != 0;
+#pragma unroll
+            for (int q = 0; q < HBB_PAIRS; ++q)
+                if (live[q]) {
+                    hp_blk_entry_add(k1[q] ? f1o : 1.0, k2[q] ? f2o : 1.0, ug[0][q][k], do_rhs[q] ? ugr[0][q][k] : 0.0,
+                                     do_rhs[q], acc0[q], racc0[q]);
+                    if (back) {
+                        any1[q] = true;
+                        hp_blk_entry_add(k1[q] ? f1n : 1.0, k2[q] ? f2n : 1.0, ug[1][q][k], do_rhs[q] ? ugr[1][q][k] : 0.0,
+                                         do_rhs[q], acc1[q], racc1[q]);
+                    }
+                }
         }
     }
-    if (live && touched) {
-        A[ia] = av;
-        if (do_rhs) rhs[(size_t)reg * P.nunk + c1] = rv;
-    }
+#pragma unroll
+    for (int q = 0; q < HBB_PAIRS; ++q)
+        if (live[q]) {
+            av[q] += -1.0 * acc0[q];
+            if (do_rhs[q]) rv[q] += -1.0 * racc0[q];
+            if (any1[q]) {                               // (a pass that involves no cell leaves the entry as it is)
+                av[q] += acc1[q];
+                if (do_rhs[q]) rv[q] += racc1[q];
+            }
+            A[ia[q]] = av[q];
+            if (do_rhs[q]) rhs[ir[q]] = rv[q];
+        }
 }
 
 // The first round's normal matrix on the f64 matrix cores (round 4).  The block of a pair of source vectors
@@ -2525,7 +2660,6 @@ __global__ __launch_bounds__(GS_THREADS) void k_hp_gram_sum_b(const hp_job* __re
     hp_gram_sum_body(J.Gp, J.need, J.active, J.G, HPJ_GUARD(J, round), J.Gold, round > 1 ? J.needlist : nullptr);
 }
 
-#define HBB_PAIRS 5
 __global__ __launch_bounds__(256) void k_hp_build_blk(const hp_plan P, const double* __restrict__ G,
                                                       const double* __restrict__ phi, const int* __restrict__ active,
                                                       const int* __restrict__ chg, int sign, double* __restrict__ A,
@@ -2534,36 +2668,41 @@ __global__ __launch_bounds__(256) void k_hp_build_blk(const hp_plan P, const dou
                                                       const double* __restrict__ Gold = nullptr,
                                                       const double* __restrict__ phiold = nullptr,
                                                       const int* __restrict__ need = nullptr) {
-    // (grid: x = HBB_PAIRS pairs of source vectors, z = region: see k_hp_build_blk_b.  A region whose last rejection
-    // changed nothing has nothing to update - sign 2 - and its workgroups leave once the hand-over words of this
-    // round's k_chol_df are cleared: 11 475 workgroups per round became 2 295, most of them gone at once)
+    // (grid: x = HBB_PAIRS pairs of source vectors, z = region: see k_hp_build_blk_b.  sign 0: the full build;
+    // sign 2: a later round's update.  A region whose last rejection changed nothing has nothing to update and its
+    // workgroups leave once the hand-over words of this round's k_chol_df are cleared: 11 475 workgroups per round
+    // became 2 295, most of them gone at once)
+    __shared__ double sh[BB_LDS];
     if (guard && *guard == 0) return;
     const int reg = blockIdx.z;
-    if (sign == 2 && chg[P.ncell + reg * (P.ncellr + 1)] == 0) {
-        if (zero && blockIdx.x == 0)
-            for (int k = threadIdx.x; k < nzero; k += 256) zero[(size_t)reg * nzero + k] = 0u;
+    if (sign == 2) {
+        hp_update_blk_body(reg, blockIdx.x * HBB_PAIRS, P, G, phi, active, chg, A, rhs, zero, nzero, Gold, phiold, need, sh);
         return;
     }
     const int npair = P.nE * (P.nE + 1) / 2;
 #pragma unroll 1
     for (int pair = blockIdx.x * HBB_PAIRS; pair < min((int)(blockIdx.x + 1) * HBB_PAIRS, npair); ++pair)
-        hp_build_blk_body(reg, pair, P, G, phi, active, chg, sign, A, rhs, guard, zero, nzero, Gold, phiold, need);
+        hp_build_blk_body(reg, pair, P, G, phi, active, A, rhs, zero, nzero, sh);
 }
 // (grid: x = HBB_PAIRS pairs of source vectors, y = job, z = region.  One workgroup per pair, job and region is
 // 183 600 workgroups for 16 jobs, most of them - every region whose last rejection changed nothing, every job that
 // has converged - without work: the launch was bound by their dispatch, 0.3 - 0.45 ms per round.  A workgroup
-// takes several pairs one after the other and leaves at once when its region has nothing to update.)
+// takes several pairs and leaves at once when its region has nothing to update.)
 __global__ __launch_bounds__(256) void k_hp_build_blk_b(const hp_plan P, const hp_job* __restrict__ jobs, int round) {
+    __shared__ double sh[BB_LDS];
     const hp_job& J = jobs[blockIdx.y];
     const int* guard = HPJ_GUARD(J, round);
     if (guard && *guard == 0) return;
     const int reg = blockIdx.z;
-    if (HPJ_REGION_IDLE(J, round, reg, P.ncell, P.ncellr)) return;
+    if (round > 1) {
+        hp_update_blk_body(reg, blockIdx.x * HBB_PAIRS, P, J.G, J.phi, J.active, J.chg, J.A0, J.rhs0, nullptr, 0, J.Gold,
+                           J.phiold, J.need, sh);
+        return;
+    }
     const int npair = P.nE * (P.nE + 1) / 2;
 #pragma unroll 1
     for (int pair = blockIdx.x * HBB_PAIRS; pair < min((int)(blockIdx.x + 1) * HBB_PAIRS, npair); ++pair)
-        hp_build_blk_body(reg, pair, P, J.G, J.phi, J.active, J.chg, round == 1 ? 0 : 2, J.A0, J.rhs0, guard,
-                          nullptr, 0, J.Gold, J.phiold, J.need);
+        hp_build_blk_body(reg, pair, P, J.G, J.phi, J.active, J.A0, J.rhs0, nullptr, 0, sh);
 }
 
 __global__ __launch_bounds__(256) void k_hp_build_mfma(const hp_plan P, const double* __restrict__ G,
@@ -2833,7 +2972,8 @@ __global__ void k_hp_solved(int nreg, int nunk, const double* __restrict__ stats
 
 // The validity mask of a subtraction and its two dilations (substamp footprint: `dirty`; kernel footprint: `outbad`)
 static int hp_launch_masks(zm_ctx* ctx, const hp_plan& P, const zm_hp_params* hp, const float* sci, const float* ref,
-                           const uint8_t* bpm, uint8_t* bad, uint8_t* tmp8, uint8_t* dirty, uint8_t* outbad) {
+                           const uint8_t* bpm, uint8_t* bad, uint8_t* tmp8, uint8_t* dirty, uint8_t* outbad,
+                           int* zero0 = nullptr, int nzero0 = 0, int* zero1 = nullptr, int nzero1 = 0) {
     const int nx = P.nx, ny = P.ny;
     const int64_t np = (int64_t)nx * ny;
     hipStream_t st = ctx->stream;
@@ -2857,7 +2997,8 @@ static int hp_launch_masks(zm_ctx* ctx, const hp_plan& P, const zm_hp_params* hp
     if (!split) ZM_TRY(ctx->get("hp_tmp8b", np, (void**)&tmp8b));
     if (!split && (((uintptr_t)tmp8b & 3) == 0)) {
         hipLaunchKernelGGL(k_hp_valid_rows, dim3(ny), b256, rsh, st, sci, ref, bpm, nx, ny, (float)P.il, (float)P.iu,
-                           (float)P.tl, (float)P.tu, hp->limits_dev, hp->limits_nsigma, P.hw, P.hwk, bad, tmp8, tmp8b);
+                           (float)P.tl, (float)P.tu, hp->limits_dev, hp->limits_nsigma, P.hw, P.hwk, bad, tmp8, tmp8b, zero0, nzero0,
+                           zero1, nzero1);
         if (col4) {
             hipLaunchKernelGGL(k_hp_colany4, gc4, b256, 0, st, tmp8, nx, ny, P.hw, 1, dirty);
             hipLaunchKernelGGL(k_hp_colany4, gc4, b256, 0, st, tmp8b, nx, ny, P.hwk, 1, outbad);
@@ -2867,7 +3008,8 @@ static int hp_launch_masks(zm_ctx* ctx, const hp_plan& P, const zm_hp_params* hp
         }
     } else {
         hipLaunchKernelGGL(k_hp_valid, dim3((unsigned)((np + 255) / 256)), b256, 0, st, sci, ref, bpm, np,
-                           (float)P.il, (float)P.iu, (float)P.tl, (float)P.tu, bad, hp->limits_dev, hp->limits_nsigma);
+                           (float)P.il, (float)P.iu, (float)P.tl, (float)P.tu, bad, hp->limits_dev, hp->limits_nsigma, zero0, nzero0,
+                           zero1, nzero1);
         hipLaunchKernelGGL(k_hp_rowany, dim3(ny), b256, rsh, st, bad, nx, ny, P.hw, tmp8);
         if (col4) hipLaunchKernelGGL(k_hp_colany4, gc4, b256, 0, st, tmp8, nx, ny, P.hw, 1, dirty);
         else hipLaunchKernelGGL(k_hp_colany, gc, b256, 0, st, tmp8, nx, ny, P.hw, 1, dirty);
@@ -3035,7 +3177,11 @@ extern "C" int zm_subtract_dev(zm_ctx* ctx, const float* sci, const float* sci_r
     }
 
     const dim3 b256(256);
-    ZM_TRY(hp_launch_masks(ctx, P, hp, sci, ref, bpm, bad, tmp8, dirty, outbad));
+    // the fit's counters and the rounds' flag words start at zero: the first kernel of the masks clears them for the
+    // first attempt (no fill of its own on the stream ahead of the first round), a repeat fills them itself
+    int* rflags = nullptr;
+    ZM_TRY(ctx->get("hp_rflags", sizeof(int) * 32, (void**)&rflags));        // [16] flags, [16] finished-workgroup counters
+    ZM_TRY(hp_launch_masks(ctx, P, hp, sci, ref, bpm, bad, tmp8, dirty, outbad, ibuf, HP_NIBUF, rflags, 32));
     // The fit (stamp search ... rejection rounds) is one repeatable attempt: when a barrier of the
     // fused factorisation timed out - its workgroups were not all resident, something else held
     // the GPU - every later round worked on a garbage solution, so the whole fit is run again on
@@ -3060,7 +3206,7 @@ extern "C" int zm_subtract_dev(zm_ctx* ctx, const float* sci, const float* sci_r
     for (int attempt = 0; attempt < 2; ++attempt) {
     const bool safe = attempt > 0;
     const int spin_limit = (!safe && spin_env) ? atoi(spin_env) : CF_SPIN_LIMIT;
-    ZM_HIP(hipMemsetAsync(ibuf, 0, sizeof(int) * HP_NIBUF, st));
+    if (attempt > 0) ZM_HIP(hipMemsetAsync(ibuf, 0, sizeof(int) * HP_NIBUF, st));
     ZM_TRY(hp_launch_cells(ctx, P, ref, bad, dirty, centres, active, need, ntotal));
     // LDS of k_hp_vectors
     const hv_cfg hvc = hp_vectors_cfg(P.pw, P.sw, P.npix);
@@ -3077,13 +3223,11 @@ extern "C" int zm_subtract_dev(zm_ctx* ctx, const float* sci, const float* sci_r
     // rejections to rflags[r]; every kernel of round r + 1 starts with `if (rflags[r] == 0)
     // return`, so a round enqueued in vain costs a dozen empty launches while the GPU never
     // waits for the host in between.
-    int* rflags = nullptr;
     int* h_rflags = nullptr;
     hipEvent_t* evs = nullptr;
-    ZM_TRY(ctx->get("hp_rflags", sizeof(int) * 32, (void**)&rflags));        // [16] flags, [16] finished-workgroup counters
     ZM_TRY(ctx->get_pinned("hp_rflags_h", sizeof(int) * 16, (void**)&h_rflags));
     ZM_TRY(zm_get_sync_events(ctx, 3, &evs));
-    ZM_HIP(hipMemsetAsync(rflags, 0, sizeof(int) * 32, st));
+    if (attempt > 0) ZM_HIP(hipMemsetAsync(rflags, 0, sizeof(int) * 32, st));
     // the words the rejection kernels signal through (coherent, mapped; one per round; never reset: a word counts
     // when it carries this attempt's generation)
     if (!ctx->hp_sig_h) {

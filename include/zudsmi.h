@@ -695,6 +695,57 @@ int zm_extract_measure(zm_ctx* ctx, const float* img, const float* sigma, const 
                        const int32_t* segm, int nx, int ny, const zm_wcs* wcs,
                        const zm_measure_params* params, int n, const zm_object* rows, zm_object_ext* out);
 
+/* ---- second pass with MASK_TYPE BLANK / CORRECT (opt-in) ---------------------- */
+/* MASK_TYPE of sextractor.conf.  zm_extract_measure[_dev] and its results are what they were.  These measure the same
+ * columns, and the aperture of the first pass again, with the pixels of other objects and the object's own bad pixels
+ * taken out ("MASK_TYPE"; restated in tests/mask_ref.py).  For the object with NUMBER n a pixel inside the
+ * frame is unusable when it is bad (the rule of zm_extract) or when segm is neither 0 nor n.  CORRECT: an unusable pixel
+ * takes value and sigma of its mirror about the centre, (floor(2 cx - i + 0.5), floor(2 cy - j + 0.5)), where that lies
+ * inside the frame and is usable for n (counted as replaced); otherwise, and always under BLANK, it adds nothing to any
+ * sum (counted as lost).  Weights that depend on position are taken at the pixel itself.  The centre is the isophotal
+ * barycentre for the Kron sums and the aperture, the current centre of every pass for the window.  An object without an
+ * unusable pixel in its footprints gets the zm_object_ext row of zm_extract_measure bit for bit. */
+#define ZM_MASK_BLANK 1
+#define ZM_MASK_CORRECT 2
+typedef struct zm_mask_params {
+    int32_t type;            /* ZM_MASK_BLANK or ZM_MASK_CORRECT */
+    int32_t pad_;
+    double aper_radius;      /* radius of the aperture, pixels: zm_extract_params.aper_radius of the first pass, in (0, 512) */
+} zm_mask_params;
+void zm_mask_params_default(zm_mask_params* p);      /* CORRECT, 3.0 */
+
+#define ZM_AUTO_CROWDED 8        /* flags_auto (masked pass only): 10 (nrepl + nlost) > npix + nlost */
+
+/* One row of the masked pass beside its zm_object_ext.  In the ext row npix_auto counts the pixels summed, replaced ones
+ * included, and nskip_auto the lost ones; ZM_AUTO_SKIPPED, _OFFFRAME and _MINRADIUS keep their formulas. */
+typedef struct zm_object_mask {
+    int32_t number;
+    int32_t nrepl_auto;      /* Kron ellipse: pixels replaced by their mirror */
+    int32_t nlost_auto;      /* ... pixels left out (= nskip_auto) */
+    int32_t nap;             /* aperture: pixels inside the frame that overlap the circle */
+    int32_t nrepl_aper;      /* ... of these replaced */
+    int32_t nlost_aper;      /* ... of these left out */
+    int32_t nrepl_win;       /* window, final pass, pixels that overlap its circle: replaced */
+    int32_t nlost_win;       /* ... left out */
+    int32_t crowded;         /* 1: ZM_AUTO_CROWDED is set or 10 (nrepl_aper + nlost_aper) > nap */
+    int32_t pad_;
+    double flux_aper;        /* sum of overlap x value over the aperture, lost pixels left out (the first pass sums bad
+                              * pixels' values and only flags them) */
+    double fluxerr_aper;     /* sqrt(sum of overlap x sigma^2) */
+} zm_object_mask;
+
+/* The arguments of zm_extract_measure_dev, then the mask parameters and out_mask (host array of n rows).  A type other
+ * than BLANK or CORRECT or a radius outside (0, 512) is an error.  n = 0 returns success and writes nothing. */
+int zm_extract_measure_masked_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                                  const int32_t* segm_dev, int nx, int ny, const zm_wcs* wcs,
+                                  const zm_measure_params* params, int n, const zm_object* rows, zm_object_ext* out,
+                                  const zm_mask_params* mask, zm_object_mask* out_mask);
+/* The same with host planes. */
+int zm_extract_measure_masked(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                              const int32_t* segm, int nx, int ny, const zm_wcs* wcs,
+                              const zm_measure_params* params, int n, const zm_object* rows, zm_object_ext* out,
+                              const zm_mask_params* mask, zm_object_mask* out_mask);
+
 /* ---- detection thumbnails: stamps of several planes on one grid --------------- */
 /* Replaces the thumbnail step of the subtraction driver (scripts/dosub.py:133-150 -> zuds/thumbnails.py:54-94,133-146):
  * two whole-frame SWarp runs (sub.aligned_to(ref), sci.aligned_to(ref)) and a Cutout2D per detection and image, and the

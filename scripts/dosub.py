@@ -2,7 +2,8 @@
 """Make subtractions: the driver of the reference's ``scripts/dosub.py``
 (``do_one``), database-free.
 
-usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns] [--deblend] [--clean [--clean-param X]]
+usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns [--mask-type blank|correct]] [--deblend]
+                                        [--clean [--clean-param X]]
                                         [--rb-model BASE [--rb-cut X]]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
@@ -13,6 +14,11 @@ With ``--param-columns`` (needs ``--detect``) the catalog holds every column of 
 ``XWIN_WORLD``, ... : ``extract.PARAM_COLUMNS``) and the ds9 region file ``sub.*.reg`` is written next to it
 once the detections have been filtered (``PipelineRegionFile.from_catalog``: green where ``GOODCUT`` is set, red
 elsewhere).
+With ``--mask-type blank|correct`` (needs ``--param-columns``) the Kron, windowed and aperture sums of the wide table leave
+out the pixels of other objects and the object's own bad pixels, or with ``correct`` take their mirrors about the centre
+instead (``MASK_TYPE`` of ``sextractor.conf``; the map is the final one, after ``--deblend`` and ``--clean``): the catalog's
+header says ``ZMMASKTY = 'BLANK'`` or ``'CORRECT'``, its table carries ``NREPL_*`` / ``NLOST_*``, and the S/N cut reads the
+masked ``FLUX_APER`` / ``FLUXERR_APER``.
 With ``--deblend`` (needs ``--detect``) the extraction deblends (``DEBLEND_NTHRESH`` 32, ``DEBLEND_MINCONT`` 0.005): the
 catalog's header says ``ZMDEBLND = T`` and its table carries ``PARENT_NUMBER``.
 With ``--clean`` (needs ``--detect``) the extraction ends with the CLEAN pass (``CLEAN_PARAM`` 1.0, or ``--clean-param X``):
@@ -79,7 +85,7 @@ def write_stamps(sub, detections, stamps, size=None):
 
 
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
-           rb_cut=None, deblend=False, clean=False):
+           rb_cut=None, deblend=False, clean=False, mask=None):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -122,7 +128,7 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
     if detect:
         catstart = time.time()
         cat = zuds.PipelineFITSCatalog.from_image(sub, columns='param' if param_columns else 'isophotal',
-                                                   deblend=deblend, clean=clean)
+                                                   deblend=deblend, clean=clean, mask=mask)
         catstop = time.time()
         print(f'cat: {catstop - catstart:.2f} sec to make catalog for {sub.basename}', flush=True)
         dstart = time.time()
@@ -180,8 +186,8 @@ def main(argv):
         print('--clean-param needs --clean', file=sys.stderr)
         return 2
     argv = list(argv)
-    rb_model = rb_cut = None
-    for flag in ('--rb-model', '--rb-cut', '--clean-param'):
+    rb_model = rb_cut = mask = None
+    for flag in ('--rb-model', '--rb-cut', '--clean-param', '--mask-type'):
         if flag in argv:
             k = argv.index(flag)
             if k + 1 >= len(argv):
@@ -191,6 +197,11 @@ def main(argv):
             del argv[k:k + 2]
             if flag == '--rb-model':
                 rb_model = value
+            elif flag == '--mask-type':
+                if value not in ('blank', 'correct'):
+                    print(f'--mask-type: {value!r} is neither blank nor correct', file=sys.stderr)
+                    return 2
+                mask = value
             elif flag == '--clean-param':
                 try:
                     clean = zuds.clean_settings(dict(param=float(value)))
@@ -199,6 +210,9 @@ def main(argv):
                     return 2
             else:
                 rb_cut = float(value)
+    if mask is not None and not param_columns:
+        print('--mask-type needs --param-columns', file=sys.stderr)
+        return 2
     if (rb_model or rb_cut is not None) and not detect:
         print('--rb-model needs --detect', file=sys.stderr)
         return 2
@@ -216,7 +230,7 @@ def main(argv):
     for fn in imgs:
         try:
             do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
-                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean)
+                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

@@ -20,6 +20,11 @@ events, per call:
   bench's epoch (every object of the pass before numbered and measured, ``k_cl_stats``, the decision, and where anything
   is absorbed a second numbering and measurement); ``objects_clean`` / ``objects_deblend_clean`` what they find;
   ``crowded_clean_ms`` / ``crowded_deblend_clean_ms`` the same on the crowded field;
+* ``mask``         the masked second pass (``mask='blank' | 'correct'``: ``k_ex_kron_m``, ``k_ex_win_m``, ``k_ex_aper_m``)
+  beside the unmasked ``columns='param'`` call of the same build, per scene (``epoch``: the bench's epoch, ``crowded``:
+  the crowded field; each also with ``deblend=True``): ``param_ms`` the unmasked call, ``blank_ms`` / ``correct_ms`` the
+  masked ones, ``*_over_param`` their ratios, ``objects`` the rows measured and ``crowded_rows`` how many of them the
+  masked pass flags (FLAGS bit 1);
 * ``decide_ms``    ``zm_clean_decide`` alone (model on the host, upload, ``k_cl_pairs``, ``k_cl_resolve``, two arrays back) on
   synthetic tables of 10^3, 10^4 and 10^5 rows at the surface density of the crowded field (``decide_absorbed``: how many
   rows were absorbed); the all-pairs kernel is quadratic in the rows;
@@ -143,6 +148,26 @@ def main():
         tab, found['crowded_deblend_clean'] = eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize,
                                                               deblend=True, clean=True)
 
+    def masked_scene(call, **kw):
+        """Medians of the unmasked wide call and of both masked ones on one scene."""
+        res, seen = {}, {}
+        for key, more in (('param', {}), ('blank', dict(mask='blank')), ('correct', dict(mask='correct'))):
+            def fn():
+                seen[key] = call(columns='param', **kw, **more)
+            res[key + '_ms'] = round(clock(fn)[0], 4)
+        res['blank_over_param'] = round(res['blank_ms'] / res['param_ms'], 2)
+        res['correct_over_param'] = round(res['correct_ms'] / res['param_ms'], 2)
+        res['objects'] = int(len(seen['correct']))
+        res['crowded_rows'] = int((seen['correct']['FLAGS'] & 1).sum() - (seen['param']['FLAGS'] & 1).sum())
+        res['replaced_rows'] = int((seen['correct']['NREPL_AUTO'] > 0).sum())
+        return res
+
+    def epoch_table(**kw):
+        return sub.extract(**kw)[0]
+
+    def crowded_table(**kw):
+        return eng.extract_dev(cimg.data_ptr(), cone.data_ptr(), None, None, csize, csize, **kw)[0]
+
     def decide_table(n):
         """n synthetic rows at the crowded field's surface density (1505 objects on 1024 x 1024): one in ten bright and
         extended, the rest faint and compact."""
@@ -198,6 +223,8 @@ def main():
     edc_med, edc_min = clock(extract_deblend_clean)
     crc_med, _ = clock(crowded_clean)
     crdc_med, _ = clock(crowded_deblend_clean)
+    mask = dict(epoch=masked_scene(epoch_table), epoch_deblend=masked_scene(epoch_table, deblend=True),
+                crowded=masked_scene(crowded_table), crowded_deblend=masked_scene(crowded_table, deblend=True))
     decide_ms, decide_absorbed = {}, {}
     keep_steps = (args.steps, args.warmup)
     for n in (1000, 10000, 100000):
@@ -234,7 +261,7 @@ def main():
                objects_deblend_clean=found.get('deblend_clean'), crowded_clean_ms=round(crc_med, 4),
                crowded_deblend_clean_ms=round(crdc_med, 4), crowded_objects_clean=found.get('crowded_clean'),
                crowded_objects_deblend_clean=found.get('crowded_deblend_clean'), decide_ms=decide_ms,
-               decide_absorbed=decide_absorbed,
+               decide_absorbed=decide_absorbed, mask=mask,
                copy_ms=round(c_med, 4), copy_bytes_per_pixel=17,
                extract_over_subtract=round(e_med / s_med, 3), extract_over_copy=round(e_med / c_med, 2))
     line = json.dumps(out)

@@ -139,6 +139,18 @@ class zm_object_ext(C.Structure):
                 ('erra_world', C.c_double), ('errb_world', C.c_double), ('errtheta_world', C.c_double)]
 
 
+class zm_mask_params(C.Structure):
+    _fields_ = [('type', C.c_int32), ('pad_', C.c_int32), ('aper_radius', C.c_double)]
+
+
+class zm_object_mask(C.Structure):
+    """One row of ``zm_extract_measure_masked`` (include/zudsmi.h) beside its ``zm_object_ext``."""
+    _fields_ = [('number', C.c_int32), ('nrepl_auto', C.c_int32), ('nlost_auto', C.c_int32), ('nap', C.c_int32),
+                ('nrepl_aper', C.c_int32), ('nlost_aper', C.c_int32), ('nrepl_win', C.c_int32),
+                ('nlost_win', C.c_int32), ('crowded', C.c_int32), ('pad_', C.c_int32),
+                ('flux_aper', C.c_double), ('fluxerr_aper', C.c_double)]
+
+
 class zm_stamp_plane(C.Structure):
     """One source plane of ``zm_stamps`` / ``zm_stamps_dev`` (include/zudsmi.h)."""
     _fields_ = [('img', C.c_void_p), ('wcs', zm_wcs), ('fscale', C.c_double),
@@ -181,6 +193,8 @@ STAMP_NOT_FINITE, STAMP_NO_OVERLAP = 1, 2              # zm_stamp_origin status 
 EXTRACT_CHAIN = 1                                      # zm_extract status bit (ZM_EXTRACT_CHAIN)
 EXTRACT_DEBLEND = 2                                    # zm_extract_deblend status bit (ZM_EXTRACT_DEBLEND)
 EXTRACT_CLEAN = 4                                      # zm_extract_clean status bit (ZM_EXTRACT_CLEAN)
+MASK_BLANK, MASK_CORRECT = 1, 2                        # zm_mask_params.type (ZM_MASK_*)
+AUTO_CROWDED = 8                                       # flags_auto bit of the masked pass (ZM_AUTO_CROWDED)
 HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4          # zm_hp_info.status bits (include/zudsmi.h)
 
 
@@ -310,6 +324,13 @@ _SIGS = {
                                          C.POINTER(zm_measure_params), C.c_int, _P, _P]),
     'zm_extract_measure': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
                                      C.POINTER(zm_measure_params), C.c_int, _P, _P]),
+    'zm_mask_params_default': (None, [C.POINTER(zm_mask_params)]),
+    'zm_extract_measure_masked_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
+                                                C.POINTER(zm_measure_params), C.c_int, _P, _P,
+                                                C.POINTER(zm_mask_params), _P]),
+    'zm_extract_measure_masked': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs),
+                                            C.POINTER(zm_measure_params), C.c_int, _P, _P,
+                                            C.POINTER(zm_mask_params), _P]),
     'zm_stamp_origin': (C.c_int, [C.POINTER(zm_wcs), C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     'zm_stamps_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_stamp_plane), C.POINTER(zm_wcs), C.c_int, C.c_int, _P, _P,
                                 C.c_int, _P, _P]),

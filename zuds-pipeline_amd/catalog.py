@@ -6,7 +6,9 @@ catalog is a FITS_LDAC file, as the reference asks SExtractor for (``catalog_typ
 HDU 2.  ``from_image(..., columns='param')`` asks for the wide table (``extract.PARAM_COLUMNS``: every column of
 ``sextractor.param``), which ``PipelineRegionFile.from_catalog`` needs.  ``from_image(..., deblend=, clean=)`` pass the
 two opt-in steps of the extractor on (``Engine.extract``); the table's header says which ran (``ZMDEBLND``, ``ZMCLEAN`` and
-their parameters), and ``from_file`` reads that back into ``cat.deblend`` / ``cat.clean``.
+their parameters), and ``from_file`` reads that back into ``cat.deblend`` / ``cat.clean``.  ``from_image(...,
+columns='param', mask='blank' | 'correct')`` asks for the masked second pass ("MASK_TYPE"): the wide table's
+header then says ``ZMMASKTY = 'BLANK'`` or ``'CORRECT'`` instead of ``'NONE'``, read back into ``cat.mask``.
 """
 from pathlib import Path
 
@@ -25,6 +27,13 @@ HEADER_CARDS = [('ZMDEBLND', False, 'multi-threshold deblending (not in this ver
 
 # ... and of a wide table: the Kron and windowed sums do not mask the pixels of other objects
 WIDE_CARDS = [('ZMMASKTY', 'NONE', 'MASK_TYPE of the Kron and windowed sums')]
+
+
+def wide_cards(mask=None):
+    """The cards of a wide table; ``mask``: None, 'blank' or 'correct' (the masked second pass the catalog was made with)."""
+    if not mask:
+        return list(WIDE_CARDS)
+    return [('ZMMASKTY', str(mask).upper(), 'MASK_TYPE of the Kron, windowed and aperture sums')]
 
 
 def header_cards(deblend=None, clean=None):
@@ -81,13 +90,16 @@ class PipelineFITSCatalog(File):
     image = None
     deblend = None                # dict(nthresh=, mincont=) of a catalog made with deblending
     clean = None                  # dict(param=) of a catalog made with the CLEAN pass
+    mask = None                   # 'blank' or 'correct' of a wide catalog made with the masked second pass
 
     @classmethod
-    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal', deblend=False, clean=False):
+    def from_image(cls, image, tmpdir='/tmp', kill_flagged=True, columns='isophotal', deblend=False, clean=False,
+                   mask=None):
         from .image import CalibratableImageBase
         if not isinstance(image, CalibratableImageBase):
             raise ValueError('Image is not an instance of CalibratableImage.')
-        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns, deblend=deblend, clean=clean)
+        image._call_source_extractor(tmpdir=tmpdir, catalog=True, columns=columns, deblend=deblend, clean=clean,
+                                     mask=mask)
         cat = image.catalog
         for prop in GROUP_PROPERTIES:
             setattr(cat, prop, getattr(image, prop, None))
@@ -124,6 +136,8 @@ class PipelineFITSCatalog(File):
             self.deblend = dict(nthresh=int(self.table_header['ZMDBNTHR']), mincont=float(self.table_header['ZMDBMINC']))
         if self.table_header.get('ZMCLEAN') is True:
             self.clean = dict(param=float(self.table_header['ZMCLNPAR']))
+        masked = str(self.table_header.get('ZMMASKTY', 'NONE')).strip().upper()
+        self.mask = masked.lower() if masked in ('BLANK', 'CORRECT') else None
 
     def save(self):
         try:
@@ -133,7 +147,7 @@ class PipelineFITSCatalog(File):
             self.map_to_local_file(f)
         wide = 'FLUX_AUTO' in (self.data.dtype.names or ())
         _fits.write_ldac(f, self.data, self.header or {}, self.header_comments or {},
-                         extra=header_cards(self.deblend, self.clean) + (WIDE_CARDS if wide else []))
+                         extra=header_cards(self.deblend, self.clean) + (wide_cards(self.mask) if wide else []))
 
     def kill_flagged(self):
         """Drop the detections with a bad IMAFLAGS_ISO or a bad pixel next to them (``zuds/catalog.py:132-142``); a

@@ -11,95 +11,13 @@
 // Summation as in k_ex_measure: element e of a row-major box belongs to lane e % 256, float64 partial sums per lane,
 // xor shuffles inside a wave, waves 0..3 added in order: no float atomics, the same bits on every run.  Every box is
 // clipped to the frame, so an object costs at most 3 (Kron) or 17 (window) walks over the frame.
-#include <climits>
-#include <cmath>
-
 #include "aperture_dev.h"
 
 // one rounding per operation in everything below (the per-pixel radii decide which pixels are summed: the restatement
 // evaluates the same expressions); aperture_dev.h above keeps the contraction k_aperture compiles it with
 #pragma clang fp contract(off)
 
-struct mx_obj {                      // what the kernels need of one row, prepared on the host
-    double xc, yc;                   // isophotal barycentre, 0-based
-    double cxx, cyy, cxy;            // ellipse coefficients of the isophotal moments
-    double sx, sy;                   // sqrt(x2), sqrt(y2): half extents of the unit ellipse
-    double sw, tw;                   // sigma_win, 2 sigma_win^2
-    int sx0, sx1, sy0, sy1;          // search box of the Kron radius, clipped, half-open
-    int ix0, ix1, iy0, iy1;          // the object's bounding box, clipped, half-open
-    int number, valid;               // NUMBER; 0: the moments give no ellipse (nothing is summed)
-};
-
-struct mx_kout {
-    double r1, radius, flux, var;    // first-moment radius, KRON_RADIUS, sum v, sum sigma^2
-    double sumf, e[6];               // over the members, offsets (di, dj) from the box's corner: sum of the filtered
-                                     // values; sum sigma^2 di^2, dj^2, di dj, di, dj, 1
-    int npix, nskip;
-};
-
-struct mx_wout {
-    double cx, cy;                   // final centre, 0-based
-    double m[7];                     // tv, sum w v dx^2, dy^2, dx dy, sum w^2 sigma^2 dx^2, dy^2, dx dy
-    int niter, flags;
-};
-
-__device__ __forceinline__ bool mx_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-__device__ __forceinline__ bool mx_isbad(float v, float s, unsigned b) {
-    return b != 0 || mx_nonfinite(v) || mx_nonfinite(s) || !(s > 0.f);
-}
-__device__ __forceinline__ bool mx_bad_at(const float* __restrict__ img, const float* __restrict__ sig,
-                                          const uint8_t* __restrict__ bad, size_t p) {
-    return mx_isbad(img[p], sig[p], bad ? bad[p] : 0u);
-}
-
-// a double clamped to [-1, n + 1] before it becomes an int (a double outside int's range has no defined conversion)
-__device__ __forceinline__ int mx_int(double v, int n) { return (int)fmin(fmax(v, -1.0), n + 1.0); }
-
-// the filtered value of k_ex_filter at (x, y): float32, taps in row-major order, bad and outside pixels enter as 0
-__device__ __forceinline__ float mx_filtered(const float* __restrict__ img, const float* __restrict__ sig,
-                                             const uint8_t* __restrict__ bad, int nx, int ny, int x, int y) {
-    const float coef[3][3] = {{1.f, 2.f, 1.f}, {2.f, 4.f, 2.f}, {1.f, 2.f, 1.f}};
-    float acc = 0.f;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const int xx = x + d - 1, yy = y + r - 1;
-            float v = 0.f;
-            if (xx >= 0 && xx < nx && yy >= 0 && yy < ny) {
-                const size_t p = (size_t)yy * nx + xx;
-                if (!mx_bad_at(img, sig, bad, p)) v = img[p];
-            }
-            acc += coef[r][d] * v;
-        }
-    return acc * 0.0625f;
-}
-
-__device__ __forceinline__ double mx_wsum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int mx_wsumi(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the sums of all 256 lanes, on every thread: the waves' results are added in order by everyone from the same LDS words
-template <int N>
-__device__ __forceinline__ void mx_reduce(double (&s)[N], double (*sh)[N], int lane, int wave) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) s[q] = mx_wsum(s[q]);
-    __syncthreads();                                     // the readers of the round before are done
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < N; ++q) sh[wave][q] = s[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < N; ++q) s[q] = ((sh[0][q] + sh[1][q]) + sh[2][q]) + sh[3][q];
-}
+#include "measure_dev.h"             // structs, bad-pixel rule, reduction, error sums: shared with extract_mask.hip
 
 __global__ __launch_bounds__(256) void k_ex_kron(const float* __restrict__ img, const float* __restrict__ sig,
                                                  const uint8_t* __restrict__ bad, const int* __restrict__ seg, int nx,
@@ -156,28 +74,8 @@ __global__ __launch_bounds__(256) void k_ex_kron(const float* __restrict__ img, 
     ns = mx_wsumi(ns);
     if (lane == 0) { shi[wave][0] = np; shi[wave][1] = ns; }
     // ---- walk 3: the isophotal error sums over the members -----------------------------------------------------
-    // (offsets from the box's corner are small integers and sigma^2 of a float32 has 48 bits: like the barycentre's sums
-    // these are exact in any order for all but very large objects; the shift to the barycentre happens on the host)
     double m[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    {
-        const int bw = o.ix1 - o.ix0, bh = o.iy1 - o.iy0;
-        const int total = (bw > 0 && bh > 0) ? bw * bh : 0;
-        for (int e = tid; e < total; e += 256) {
-            const int j = o.iy0 + e / bw, i = o.ix0 + e % bw;
-            const size_t p = (size_t)j * nx + i;
-            if (seg[p] != o.number) continue;
-            const double dx = i - o.ix0, dy = j - o.iy0;
-            const double sg = sig[p], sg2 = sg * sg;
-            const float fv = use_filter ? mx_filtered(img, sig, bad, nx, ny, i, j) : img[p];
-            m[0] += (double)fv;
-            m[1] += sg2 * dx * dx;
-            m[2] += sg2 * dy * dy;
-            m[3] += sg2 * dx * dy;
-            m[4] += sg2 * dx;
-            m[5] += sg2 * dy;
-            m[6] += sg2;
-        }
-    }
+    mx_iso_sums(img, sig, bad, seg, nx, ny, o, use_filter, tid, m);
     mx_reduce<7>(m, sh7, lane, wave);                    // (its barriers also publish shi)
     if (tid == 0) {
         mx_kout r;
@@ -227,9 +125,6 @@ __device__ __forceinline__ void mx_win_pass(const float* __restrict__ img, const
         }
     }
 }
-
-#define MX_WIN_ITER 16
-#define MX_WIN_STEP2 1e-8            // (1e-4 px)^2
 
 __global__ __launch_bounds__(256) void k_ex_win(const float* __restrict__ img, const float* __restrict__ sig,
                                                 const uint8_t* __restrict__ bad, int nx, int ny,
@@ -297,21 +192,20 @@ static int mx_clip(double v, int n) {                    // v rounded down into 
     return (int)v;
 }
 
-extern "C" int zm_extract_measure_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
-                                      const int32_t* segm_dev, int nx, int ny, const zm_wcs* wcs,
-                                      const zm_measure_params* params, int n, const zm_object* rows,
-                                      zm_object_ext* out) {
-    ZM_CHECK(ctx && img && sigma && segm_dev && params, "zm_extract_measure: null argument");
-    ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30, "zm_extract_measure: bad sizes %d x %d", nx, ny);
-    ZM_CHECK(n >= 0 && n <= (1 << 24), "zm_extract_measure: bad row count %d", n);
+int mx_check_args(const char* who, const zm_ctx* ctx, const float* img, const float* sigma, const int32_t* segm_dev,
+                  int nx, int ny, const zm_measure_params* params, int n) {
+    ZM_CHECK(ctx && img && sigma && segm_dev && params, "%s: null argument", who);
+    ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30, "%s: bad sizes %d x %d", who, nx, ny);
+    ZM_CHECK(n >= 0 && n <= (1 << 24), "%s: bad row count %d", who, n);
     ZM_CHECK(params->kron_fact > 0 && params->kron_min_radius > 0 && params->kron_fact < 1e6 &&
                  params->kron_min_radius < 1e6 && (params->filter == 0 || params->filter == 1),
-             "zm_extract_measure: bad parameters (PHOT_AUTOPARAMS %g, %g; filter %d)", params->kron_fact,
+             "%s: bad parameters (PHOT_AUTOPARAMS %g, %g; filter %d)", who, params->kron_fact,
              params->kron_min_radius, params->filter);
-    if (n == 0) return 0;
-    ZM_CHECK(rows && out, "zm_extract_measure: %d rows need a row array and an output array", n);
-    ZM_HIP(hipSetDevice(ctx->device));
-    std::vector<mx_obj> objs(n);
+    return 0;
+}
+
+void mx_prepare(const zm_object* rows, int n, int nx, int ny, std::vector<mx_obj>& objs) {
+    objs.resize(n);
     for (int k = 0; k < n; ++k) {
         const zm_object& r = rows[k];
         mx_obj& o = objs[k];
@@ -343,6 +237,18 @@ extern "C" int zm_extract_measure_dev(zm_ctx* ctx, const float* img, const float
         o.iy1 = mx_clip((double)r.ymax, ny);
         o.number = r.number;
     }
+}
+
+extern "C" int zm_extract_measure_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                                      const int32_t* segm_dev, int nx, int ny, const zm_wcs* wcs,
+                                      const zm_measure_params* params, int n, const zm_object* rows,
+                                      zm_object_ext* out) {
+    ZM_TRY(mx_check_args("zm_extract_measure", ctx, img, sigma, segm_dev, nx, ny, params, n));
+    if (n == 0) return 0;
+    ZM_CHECK(rows && out, "zm_extract_measure: %d rows need a row array and an output array", n);
+    ZM_HIP(hipSetDevice(ctx->device));
+    std::vector<mx_obj> objs;
+    mx_prepare(rows, n, nx, ny, objs);
     char* d = nullptr;
     const size_t b_obj = ((size_t)n * sizeof(mx_obj) + 15) & ~(size_t)15, b_k = ((size_t)n * sizeof(mx_kout) + 15) & ~(size_t)15;
     ZM_TRY(ctx->get("mx_buf", b_obj + b_k + (size_t)n * sizeof(mx_wout), (void**)&d));
@@ -359,6 +265,11 @@ extern "C" int zm_extract_measure_dev(zm_ctx* ctx, const float* img, const float
     ZM_HIP(hipMemcpyAsync(kout.data(), d_k, (size_t)n * sizeof(mx_kout), hipMemcpyDeviceToHost, ctx->stream));
     ZM_HIP(hipMemcpyAsync(wout.data(), d_w, (size_t)n * sizeof(mx_wout), hipMemcpyDeviceToHost, ctx->stream));
     ZM_HIP(hipStreamSynchronize(ctx->stream));
+    return mx_finish(rows, n, nx, ny, wcs, objs, kout, wout, out);
+}
+
+int mx_finish(const zm_object* rows, int n, int nx, int ny, const zm_wcs* wcs, const std::vector<mx_obj>& objs,
+              const std::vector<mx_kout>& kout, const std::vector<mx_wout>& wout, zm_object_ext* out) {
     for (int k = 0; k < n; ++k) {
         const zm_object& r = rows[k];
         const mx_obj& o = objs[k];
@@ -453,26 +364,33 @@ extern "C" int zm_extract_measure_dev(zm_ctx* ctx, const float* img, const float
     return 0;
 }
 
+int mx_stage(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* segm, int nx, int ny,
+             float** d_img, float** d_sig, uint8_t** d_bad, int32_t** d_seg) {
+    ZM_HIP(hipSetDevice(ctx->device));
+    const size_t np = (size_t)nx * ny;
+    *d_bad = nullptr;
+    ZM_TRY(ctx->get("h_img", np * 4, (void**)d_img));
+    ZM_TRY(ctx->get("h_wgt", np * 4, (void**)d_sig));
+    ZM_TRY(ctx->get("ex_seg", np * 4, (void**)d_seg));
+    ZM_HIP(hipMemcpyAsync(*d_img, img, np * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZM_HIP(hipMemcpyAsync(*d_sig, sigma, np * 4, hipMemcpyHostToDevice, ctx->stream));
+    ZM_HIP(hipMemcpyAsync(*d_seg, segm, np * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (bad) {
+        ZM_TRY(ctx->get("h_bpm", np, (void**)d_bad));
+        ZM_HIP(hipMemcpyAsync(*d_bad, bad, np, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return 0;
+}
+
 extern "C" int zm_extract_measure(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
                                   const int32_t* segm, int nx, int ny, const zm_wcs* wcs,
                                   const zm_measure_params* params, int n, const zm_object* rows, zm_object_ext* out) {
     ZM_CHECK(ctx && img && sigma && segm, "zm_extract_measure: null argument");
     ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30, "zm_extract_measure: bad sizes %d x %d", nx, ny);
     if (n == 0) return 0;
-    ZM_HIP(hipSetDevice(ctx->device));
-    const size_t np = (size_t)nx * ny;
     float *d_img = nullptr, *d_sig = nullptr;
     uint8_t* d_bad = nullptr;
     int32_t* d_seg = nullptr;
-    ZM_TRY(ctx->get("h_img", np * 4, (void**)&d_img));
-    ZM_TRY(ctx->get("h_wgt", np * 4, (void**)&d_sig));
-    ZM_TRY(ctx->get("ex_seg", np * 4, (void**)&d_seg));
-    ZM_HIP(hipMemcpyAsync(d_img, img, np * 4, hipMemcpyHostToDevice, ctx->stream));
-    ZM_HIP(hipMemcpyAsync(d_sig, sigma, np * 4, hipMemcpyHostToDevice, ctx->stream));
-    ZM_HIP(hipMemcpyAsync(d_seg, segm, np * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (bad) {
-        ZM_TRY(ctx->get("h_bpm", np, (void**)&d_bad));
-        ZM_HIP(hipMemcpyAsync(d_bad, bad, np, hipMemcpyHostToDevice, ctx->stream));
-    }
+    ZM_TRY(mx_stage(ctx, img, sigma, bad, segm, nx, ny, &d_img, &d_sig, &d_bad, &d_seg));
     return zm_extract_measure_dev(ctx, d_img, d_sig, d_bad, d_seg, nx, ny, wcs, params, n, rows, out);
 }

@@ -236,18 +236,19 @@ class DeviceSubtraction(object):
             self.check_limits()
         return self.info
 
-    def extract(self, wcs=None, max_objects=None, deblend=False, clean=False, **params):
+    def extract(self, wcs=None, max_objects=None, deblend=False, clean=False, mask=None, **params):
         """Detection catalog of the resident difference image (``Engine.extract_dev``): noise plane as sigma, the
         subtraction mask as flag plane, its ``BAD_SUM`` pixels as bad pixels; nothing but the object table crosses to
         the host.  No background pass: hotpants' difference image carries none.  ``wcs``: the science grid unless
         given.  ``columns='param'`` (passed on with ``params``, as kron_fact / kron_min_radius are): the wide table of
         ``extract.PARAM_COLUMNS``.  ``deblend``: False, True or dict(nthresh=, mincont=), as for ``Engine.extract``: the
         table then carries PARENT_NUMBER.  ``clean``: False, True or dict(param=), the CLEAN pass of ``Engine.extract``: the
-        table then carries NMERGED.  Returns (table, number found, segmentation map as an int32 tensor)."""
+        table then carries NMERGED.  ``mask``: None, 'blank' or 'correct' (needs ``columns='param'``), the masked second
+        pass of ``Engine.extract``.  Returns (table, number found, segmentation map as an int32 tensor)."""
         torch = self.torch
         self.result()
         ny, nx = self.shape
-        kw = dict(params, deblend=deblend, clean=clean)
+        kw = dict(params, deblend=deblend, clean=clean, mask=mask)
         if max_objects is not None:
             kw['max_objects'] = max_objects
         with torch.cuda.stream(self.stream):
@@ -259,7 +260,7 @@ class DeviceSubtraction(object):
         return tab, nfound, segm
 
     def candidates(self, seeing, wcs=None, max_objects=None, rb_model=None, sci=None, ref=None, fid=None, rb_cut=None,
-                   sci_flxscale=1.0, deblend=False, clean=False, **extract_params):
+                   sci_flxscale=1.0, deblend=False, clean=False, mask=None, **extract_params):
         """The filtered detection table of the resident difference image: ``extract``, the ``kill_flagged`` rule of
         ``PipelineFITSCatalog`` (``IMAFLAGS_ISO & BAD_SUM == 0`` and ``FLAGS_WEIGHT == 0``), the pixel cuts on the
         resident ``diff`` / ``noise`` / ``submask`` (``filterobjects.pixel_cuts_dev``) and ``filter_table`` - what
@@ -267,7 +268,8 @@ class DeviceSubtraction(object):
         object table, the positions and the per-candidate results are all that crosses PCIe.  ``seeing``: the science
         FWHM in pixels.  ``columns='param'`` among ``extract_params`` keeps the wide table's columns (the cuts read only
         columns both tables have); ``deblend``: as for ``extract`` (FLAGS 2 passes the cuts: the reference's is
-        ``FLAGS > 2``); ``clean``: as for ``extract``: the cuts then see the merged objects alone.  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found).
+        ``FLAGS > 2``); ``clean``: as for ``extract``: the cuts then see the merged objects alone; ``mask``: as for ``extract``: the S/N
+        cut then reads the masked FLUX_APER / FLUXERR_APER.  Returns (table with GOODCUT / BPMCUT / RMSCUT / rb, number of objects found).
         ``rb_model`` (``realbogus.RBModel``; needs ``sci`` and ``ref``, the tensors handed to ``run``): behind the pixel
         cuts the surviving rows are stamped on this chain's stream (``zm_stamps_dev``), scored where the blocks lie
         (``zm_rb_score_dev``) and cut at ``rb_cut`` or ``RB_CUT[fid]`` (``zuds/filterobjects.py:196-240``); ``rb[n]`` is
@@ -277,7 +279,8 @@ class DeviceSubtraction(object):
             if sci is None or ref is None:
                 raise ValueError('candidates(rb_model=...) needs the sci and ref tensors for the stamps')
             cut = rb_cut_for(fid, rb_cut)
-        tab, nfound, _ = self.extract(wcs=wcs, max_objects=max_objects, deblend=deblend, clean=clean, **extract_params)
+        tab, nfound, _ = self.extract(wcs=wcs, max_objects=max_objects, deblend=deblend, clean=clean, mask=mask,
+                                      **extract_params)
         tab = tab[((tab['IMAFLAGS_ISO'] & self.BAD_SUM) == 0) & (tab['FLAGS_WEIGHT'] == 0)]
         self.engine.set_stream(self.stream.cuda_stream)
         with self.torch.cuda.stream(self.stream):

@@ -9,7 +9,9 @@ they use the context's one stream and scratch buffers: one call at a time per en
 Two steps of ``sextractor.conf`` are opt-in keywords of both calls: ``deblend=True | dict(nthresh=, mincont=)``
 (multi-threshold deblending; the table gains PARENT_NUMBER) and ``clean=True | dict(param=)`` (the CLEAN pass on the
 objects of the pass before; the table gains NMERGED).  ``Engine.clean_decide`` is CLEAN's decision alone on a table,
-``Engine.clean_stats`` the per-object sums of the last ``clean=`` call.
+``Engine.clean_stats`` the per-object sums of the last ``clean=`` call.  A third, ``MASK_TYPE``, belongs to the wide
+table: ``columns='param', mask='blank' | 'correct'`` runs the masked second pass (``zm_extract_measure_masked``; the table
+gains ``MASK_COLUMNS`` and its FLUX_APER / FLUXERR_APER are the masked values).
 """
 import ctypes as C
 import threading
@@ -21,7 +23,7 @@ from ._lib import as_f32, as_i32, check, ptr, wcs_struct
 from .engine import Engine
 
 __all__ = ['CATALOG_COLUMNS', 'PARAM_COLUMNS', 'extract_params', 'measure_params', 'deblend_params', 'deblend_settings',
-           'clean_params', 'clean_settings', 'TooManyDetectionsError']
+           'clean_params', 'clean_settings', 'mask_params', 'mask_setting', 'MASK_COLUMNS', 'TooManyDetectionsError']
 
 # column of the catalog <- field of zm_object (include/zudsmi.h); columns that are not computed are absent
 CATALOG_COLUMNS = [('NUMBER', 'number', 'i4'), ('X_IMAGE', 'x_image', 'f8'), ('Y_IMAGE', 'y_image', 'f8'),
@@ -51,6 +53,11 @@ EXT_COLUMNS = [('MAG_AUTO', 'mag_auto', 'f8'), ('MAGERR_AUTO', 'magerr_auto', 'f
 PARAM_COLUMNS = CATALOG_COLUMNS + EXT_COLUMNS
 PARAM_DTYPE = np.dtype([(c, t) for c, _, t in PARAM_COLUMNS])
 COLUMN_SETS = ('isophotal', 'param')
+# what a masked second pass (mask='blank' | 'correct') adds to the wide table; column <- field of zm_object_mask
+MASK_COLUMNS = [('NREPL_AUTO', 'nrepl_auto', 'i4'), ('NLOST_AUTO', 'nlost_auto', 'i4'),
+                ('NREPL_APER', 'nrepl_aper', 'i4'), ('NLOST_APER', 'nlost_aper', 'i4'),
+                ('NREPL_WIN', 'nrepl_win', 'i4'), ('NLOST_WIN', 'nlost_win', 'i4')]
+MASK_TYPES = {'blank': _lib.MASK_BLANK, 'correct': _lib.MASK_CORRECT}
 
 
 class TooManyDetectionsError(Exception):
@@ -142,6 +149,29 @@ def clean_params(clean=True):
     return p
 
 
+def mask_setting(mask=None):
+    """``None`` (the plain second pass) or 'blank' / 'correct' from ``mask=None | 'none' | 'blank' | 'correct'`` (any
+    case: MASK_TYPE of sextractor.conf is upper case); anything else raises ValueError."""
+    if mask is None or mask is False:
+        return None
+    if isinstance(mask, str) and mask.strip().lower() == 'none':
+        return None
+    if not isinstance(mask, str) or mask.strip().lower() not in MASK_TYPES:
+        raise ValueError(f"mask={mask!r}: None, 'blank' or 'correct'")
+    return mask.strip().lower()
+
+
+def mask_params(mask, aper_radius=3.0):
+    """``None`` or the zm_mask_params of ``mask_setting(mask)`` with the aperture radius of the first pass."""
+    kind = mask_setting(mask)
+    if kind is None:
+        return None
+    p = _lib.zm_mask_params()
+    _lib.lib().zm_mask_params_default(C.byref(p))
+    p.type, p.aper_radius = MASK_TYPES[kind], float(aper_radius)
+    return p
+
+
 def with_column(tab, name, values):
     """``tab`` with one more int32 column."""
     out = np.zeros(len(tab), dtype=np.dtype(tab.dtype.descr + [(name, 'i4')]))
@@ -156,15 +186,19 @@ def with_parent(tab, parent):
     return with_column(tab, 'PARENT_NUMBER', parent)
 
 
-def _split_params(columns, params):
-    """(extraction keywords, zm_measure_params or None) of a call's ``columns`` and keyword arguments."""
+def _split_params(columns, params, mask=None):
+    """(extraction keywords, zm_measure_params or None, zm_mask_params or None) of a call's ``columns``, keyword
+    arguments and ``mask``."""
     if columns not in COLUMN_SETS:
         raise ValueError(f'columns={columns!r}: one of {COLUMN_SETS}')
     params = dict(params)
+    kind = mask_setting(mask)
     if columns != 'param':
-        return params, None
+        if kind is not None:
+            raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
+        return params, None, None
     mp = measure_params(params.pop('kron_fact', 2.5), params.pop('kron_min_radius', 3.5), params.get('filter', True))
-    return params, mp
+    return params, mp, mask_params(kind, params.get('aper_radius', 3.0))
 
 
 def ext_to_table(rows, ext, n):
@@ -179,14 +213,37 @@ def ext_to_table(rows, ext, n):
     return tab.view(np.recarray), rext.copy().view(np.recarray)
 
 
-def _measure(self, fn, what, img, sigma, bad, segm, nx, ny, wcs, mp, n):
-    """The second pass on the rows the extraction of this thread has just written: (wide table, zm_object_ext rows)."""
+def masked_table(rows, ext, msk, n):
+    """The wide table of a masked second pass from the first n rows of a zm_object array, its zm_object_ext array and its
+    zm_object_mask array: FLUX_APER / FLUXERR_APER are the masked values, FLAGS gains bit 1 where ``crowded`` is set, and
+    ``MASK_COLUMNS`` are added.  Returns (table, ext rows, mask rows)."""
+    wide, rext = ext_to_table(rows, ext, n)
+    rmsk = np.frombuffer(msk, dtype=np.dtype(_lib.zm_object_mask), count=n) if n else np.zeros(0, np.dtype(_lib.zm_object_mask))
+    tab = np.zeros(n, dtype=np.dtype(wide.dtype.descr + [(c, t) for c, _, t in MASK_COLUMNS]))
+    for c in wide.dtype.names:
+        tab[c] = wide[c]
+    tab['FLUX_APER'], tab['FLUXERR_APER'] = rmsk['flux_aper'], rmsk['fluxerr_aper']
+    tab['FLAGS'] |= (rmsk['crowded'] != 0).astype(np.int32)
+    for col, field, _ in MASK_COLUMNS:
+        tab[col] = rmsk[field]
+    return tab.view(np.recarray), rext, rmsk.copy().view(np.recarray)
+
+
+def _measure(self, dev, img, sigma, bad, segm, nx, ny, wcs, mp, n, mk=None):
+    """The second pass on the rows the extraction of this thread has just written: (wide table, zm_object_ext rows,
+    zm_object_mask rows or None).  ``dev``: device planes; ``mk``: the zm_mask_params of a masked pass."""
     rows = self.__dict__['_extract_rows'][threading.get_ident()]
     ext = (_lib.zm_object_ext * max(n, 1))()
     w = wcs_struct(wcs) if wcs is not None else None
-    check(fn(self._ctx, img, sigma, bad, segm, nx, ny, C.byref(w) if w is not None else None, C.byref(mp), int(n),
-             C.cast(rows, C.c_void_p), C.cast(ext, C.c_void_p)), what)
-    return ext_to_table(rows, ext, n)
+    what = 'zm_extract_measure' + ('_masked' if mk is not None else '') + ('_dev' if dev else '')
+    args = (self._ctx, img, sigma, bad, segm, nx, ny, C.byref(w) if w is not None else None, C.byref(mp), int(n),
+            C.cast(rows, C.c_void_p), C.cast(ext, C.c_void_p))
+    if mk is None:
+        check(getattr(self.L, what)(*args), what)
+        return ext_to_table(rows, ext, n) + (None,)
+    msk = (_lib.zm_object_mask * max(n, 1))()
+    check(getattr(self.L, what)(*args, C.byref(mk), C.cast(msk, C.c_void_p)), what)
+    return masked_table(rows, ext, msk, n)
 
 
 def rows_to_table(rows, n):
@@ -231,7 +288,7 @@ def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_object
 
 
 def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects=MAX_OBJECTS, full=False,
-                    columns='isophotal', deblend=False, clean=False, **params):
+                    columns='isophotal', deblend=False, clean=False, mask=None, **params):
     """Object table (numpy record array, columns ``CATALOG_COLUMNS``) and segmentation map (int32, 0 = sky) of ``img``
     (background already subtracted) with per-pixel noise ``sigma``, bad-pixel map ``bad`` and flag plane ``flag``.
 
@@ -251,8 +308,15 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     pass before, deblended or not: an object whose neighbour's wing explains it is folded into that neighbour, the merged
     objects are renumbered and measured on the union of their pixels, and the table gains the column NMERGED (objects
     from before CLEAN in the row; 1 = untouched).  Where nothing is absorbed, table and map are those of the same call
-    without ``clean``."""
-    params, mp = _split_params(columns, params)
+    without ``clean``.
+
+    ``mask='blank'`` or ``'correct'`` (needs ``columns='param'``): MASK_TYPE of sextractor.conf for the second pass
+    (``zm_extract_measure_masked``; DESIGN.md, "MASK_TYPE").  The Kron, windowed and aperture sums leave out the pixels of
+    other objects and the object's own bad pixels, or under ``'correct'`` take their mirror about the centre instead.
+    FLUX_APER / FLUXERR_APER are then the masked values, FLAGS gains bit 1 where a tenth of a footprint was replaced or
+    lost, the table gains ``MASK_COLUMNS``, and ``full=True`` adds ``maskrows`` (the zm_object_mask rows).  The map
+    is the final one, after ``deblend`` and ``clean``."""
+    params, mp, mk = _split_params(columns, params, mask)
     db = deblend_params(deblend)
     cl = clean_params(clean)
     img, sigma, flag = as_f32(img), as_f32(sigma), as_i32(flag)
@@ -274,12 +338,13 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     ext = None
     if mp is not None:
         first = tab
-        tab, ext = _measure(self, self.L.zm_extract_measure, 'zm_extract_measure', ptr(img), ptr(sigma), ptr(bad),
-                            ptr(segm), nx, ny, wcs, mp, len(tab))
+        tab, ext, maskrows = _measure(self, False, ptr(img), ptr(sigma), ptr(bad), ptr(segm), nx, ny, wcs, mp, len(tab), mk)
         if db is not None:
             tab = with_parent(tab, first['PARENT_NUMBER'])
         if cl is not None:
             tab = with_column(tab, 'NMERGED', first['NMERGED'])
+    if full and ext is not None and mk is not None:
+        return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext, maskrows=maskrows)
     if full and ext is not None:
         return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext)
     if full:
@@ -288,12 +353,12 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
 
 
 def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objects=MAX_OBJECTS, segm=None,
-                        columns='isophotal', deblend=False, clean=False, **params):
+                        columns='isophotal', deblend=False, clean=False, mask=None, **params):
     """The same on device planes (addresses: float32 img, sigma; uint8 bad or None; int32 flag or None; ``segm``: an
     int32 device plane that takes the segmentation map, or None).  Returns (table, number found).
     ``columns='param'`` needs the segmentation map for its second pass: without ``segm`` a plane is allocated for the
-    call.  ``deblend``, ``clean``: as for ``Engine.extract``."""
-    params, mp = _split_params(columns, params)
+    call.  ``deblend``, ``clean``, ``mask``: as for ``Engine.extract``."""
+    params, mp, mk = _split_params(columns, params, mask)
     db = deblend_params(deblend)
     cl = clean_params(clean)
     own = None
@@ -310,8 +375,8 @@ def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objec
                            int(segm) if segm else None, None, db, cl)
     if mp is not None:
         first = tab
-        tab, _ = _measure(self, self.L.zm_extract_measure_dev, 'zm_extract_measure_dev', int(img), int(sigma),
-                          int(bad) if bad else None, int(segm), int(nx), int(ny), wcs, mp, len(tab))
+        tab, _, _ = _measure(self, True, int(img), int(sigma), int(bad) if bad else None, int(segm), int(nx), int(ny),
+                             wcs, mp, len(tab), mk)
         if db is not None:
             tab = with_parent(tab, first['PARENT_NUMBER'])
         if cl is not None:

@@ -35,14 +35,14 @@ class CalibratableImageBase(FITSImage):
 
     def _call_source_extractor(self, checkimage_type=None, tmpdir='/tmp',
                                use_weightmap=True, sextractor_kws=None, catalog=False, columns='isophotal',
-                               deblend=False, clean=False):
+                               deblend=False, clean=False, mask=None):
         """Produce the requested check-images and, with ``catalog=True``, the detection catalog
         (``zuds/image.py:103-134``)."""
         from . import sextractor
         results = sextractor.run_sextractor(self, checkimage_type=checkimage_type,
                                             tmpdir=tmpdir, use_weightmap=use_weightmap,
                                             sextractor_kws=sextractor_kws, catalog=catalog, columns=columns,
-                                            deblend=deblend, clean=clean)
+                                            deblend=deblend, clean=clean, mask=mask)
         for result in results:
             if result is None:          # the catalog slot of a call that asked for check-images only
                 continue

@@ -59,10 +59,14 @@ class SubtractionJob(object):
     ``deblend`` (with ``detect``): False, True or dict(nthresh=, mincont=), the multi-threshold deblending of
     ``DeviceSubtraction.candidates``; the result then carries ``deblend``, the settings used.
     ``clean`` (with ``detect``): False, True or dict(param=), the CLEAN pass of ``DeviceSubtraction.candidates``; the
-    result then carries ``clean``, the settings used."""
+    result then carries ``clean``, the settings used.
+    ``columns`` (with ``detect``): 'isophotal' or 'param', the table of ``DeviceSubtraction.candidates``.
+    ``mask`` (with ``detect`` and ``columns='param'``): None, 'blank' or 'correct', the masked second pass of
+    ``DeviceSubtraction.candidates``; the result then carries ``mask``."""
 
     def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
-                 max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False, clean=False):
+                 max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False, clean=False,
+                 columns='isophotal', mask=None):
         if stamps and not detect:
             raise ValueError('stamps needs detect')
         if rb_model is not None:
@@ -74,7 +78,16 @@ class SubtractionJob(object):
             raise ValueError('deblend needs detect')
         if clean and not detect:
             raise ValueError('clean needs detect')
-        from .extract import clean_settings, deblend_settings
+        from .extract import COLUMN_SETS, clean_settings, deblend_settings, mask_setting
+        if columns not in COLUMN_SETS:
+            raise ValueError(f'columns={columns!r}: one of {COLUMN_SETS}')
+        if columns != 'isophotal' and not detect:
+            raise ValueError('columns needs detect')
+        self.columns, self.mask = columns, mask_setting(mask)
+        if self.mask is not None and not detect:
+            raise ValueError('mask needs detect')
+        if self.mask is not None and columns != 'param':
+            raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
         self.deblend = deblend_settings(deblend)         # (raises on settings the extractor refuses)
         self.clean = clean_settings(clean)
         self.rb_model, self.fid, self.rb_cut = rb_model, fid, rb_cut
@@ -186,6 +199,10 @@ def _detect(ch, job, out):
             dbkw['deblend'] = out['deblend'] = job.deblend
         if getattr(job, 'clean', None):
             dbkw['clean'] = out['clean'] = job.clean
+        if getattr(job, 'columns', 'isophotal') != 'isophotal':
+            dbkw['columns'] = job.columns
+        if getattr(job, 'mask', None):
+            dbkw['mask'] = out['mask'] = job.mask
         cat, nfound = ch.candidates(float(sci['seeing']), wcs=sci['wcs'], **rbkw, **dbkw)
     except _lib.ZMError as exc:
         out['cat'], out['detect_error'] = None, str(exc)

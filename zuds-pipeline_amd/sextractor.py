@@ -9,11 +9,13 @@ filter ``default.conv``, ``DETECT_THRESH`` 1.5, ``DETECT_MINAREA`` 5, no deblend
 ``dict(nthresh=, mincont=)``) opts into the multi-threshold deblending of DESIGN.md ("Deblending"); only then may
 ``sextractor_kws`` carry ``DEBLEND_NTHRESH`` and ``DEBLEND_MINCONT``.  ``clean=True`` (or ``dict(param=)``) opts into the
 CLEAN pass of DESIGN.md ("CLEAN"); only then may ``sextractor_kws`` carry ``CLEAN`` (which must say yes) and
-``CLEAN_PARAM``.
+``CLEAN_PARAM``.  ``mask='blank' | 'correct'`` (with ``columns='param'``) opts into the masked second pass of DESIGN.md
+("MASK_TYPE"); only then may ``sextractor_kws`` carry ``MASK_TYPE`` (``NONE``, ``BLANK`` or ``CORRECT``), which overrides
+the keyword.
 
 ``sextractor_kws``: ``DETECT_THRESH``, ``DETECT_MINAREA``, ``FILTER``, ``PHOT_APERTURES`` (one diameter),
 ``SATUR_LEVEL``, ``BACK_SIZE``, ``BACK_FILTERSIZE`` are honoured; keys that would change something this version does
-not do (``DEBLEND_*`` without ``deblend=True``, ``CLEAN*`` without ``clean=True``, ``MASK_TYPE``, ``FILTER_NAME``, a ``WEIGHT_TYPE`` other than
+not do (``DEBLEND_*`` without ``deblend=True``, ``CLEAN*`` without ``clean=True``, ``MASK_TYPE`` without ``mask=``, ``FILTER_NAME``, a ``WEIGHT_TYPE`` other than
 ``MAP_WEIGHT``, an ``ANALYSIS_THRESH`` different from ``DETECT_THRESH``) raise ``ValueError``; bookkeeping keys are ignored.
 ``columns='param'`` asks for the wide table (``extract.PARAM_COLUMNS``: every column of ``sextractor.param``); only then
 may ``sextractor_kws`` carry ``PHOT_AUTOPARAMS`` (two values).
@@ -50,13 +52,16 @@ def _yes(v):
 _DEBLEND_KEYS = {'DEBLEND_NTHRESH': 'nthresh', 'DEBLEND_MINCONT': 'mincont'}
 
 
-def extraction_settings(sextractor_kws=None, header=None, deblend=False, clean=False):
+def extraction_settings(sextractor_kws=None, header=None, deblend=False, clean=False, mask=None):
     """Keyword arguments of ``Engine.extract`` from ``sextractor_kws`` and the image header (``SATURATE``).
     ``deblend``: False, True or dict(nthresh=, mincont=); only when it is set are ``DEBLEND_NTHRESH`` and
     ``DEBLEND_MINCONT`` accepted (they override the dict), and the result then carries ``deblend``.
     ``clean``: False, True or dict(param=); only when it is set are ``CLEAN`` (which must say yes: the keyword asked for the
-    pass) and ``CLEAN_PARAM`` (which overrides the dict) accepted, and the result then carries ``clean``."""
-    from .extract import clean_settings, deblend_settings
+    pass) and ``CLEAN_PARAM`` (which overrides the dict) accepted, and the result then carries ``clean``.
+    ``mask``: None, 'blank' or 'correct'; only when it is set is ``MASK_TYPE`` accepted (``NONE``, ``BLANK`` or ``CORRECT``:
+    it overrides the keyword, ``NONE`` meaning the plain second pass), and the result then carries ``mask`` ('blank',
+    'correct', or None after ``NONE``)."""
+    from .extract import clean_settings, deblend_settings, mask_setting
     kws = {str(k).upper(): v for k, v in (sextractor_kws or {}).items()}
     db = deblend_settings(deblend)
     if db is not None:
@@ -70,10 +75,17 @@ def extraction_settings(sextractor_kws=None, header=None, deblend=False, clean=F
         if 'CLEAN_PARAM' in kws:
             cl['param'] = kws.pop('CLEAN_PARAM')
         cl = clean_settings(cl)
+    asked = mask_setting(mask) is not None
+    mk = mask_setting(mask)
+    if asked and 'MASK_TYPE' in kws:
+        v = kws.pop('MASK_TYPE')
+        if not isinstance(v, str) or v.strip().upper() not in ('NONE', 'BLANK', 'CORRECT'):
+            raise ValueError(f'sextractor_kws: MASK_TYPE {v!r} must be NONE, BLANK or CORRECT')
+        mk = mask_setting(v)
     for k in kws:
         if k in _REFUSED or k.startswith(_REFUSED_PREFIXES):
             raise ValueError(f'sextractor_kws: {k} would change a step this extractor does not have '
-                             f'(deblending needs deblend=True, cleaning clean=True; mask correction and other filters '
+                             f'(deblending needs deblend=True, cleaning clean=True, masking mask=; other filters '
                              f'are not in this version)')
         if k not in _HONOURED and k not in _IGNORED:
             raise ValueError(f'sextractor_kws: unknown key {k}')
@@ -93,6 +105,8 @@ def extraction_settings(sextractor_kws=None, header=None, deblend=False, clean=F
         out['deblend'] = db
     if cl is not None:
         out['clean'] = cl
+    if asked:
+        out['mask'] = mk
     return out
 
 
@@ -146,7 +160,7 @@ def measurement_settings(sextractor_kws=None):
     return rest, dict(kron_fact=float(auto[0]), kron_min_radius=float(auto[1]))
 
 
-def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=False, clean=False):
+def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=False, clean=False, mask=None):
     """(PipelineFITSCatalog, segmentation map) of the background-subtracted plane ``sub``: noise = the image's
     rms_image, bad = weight 0, flags = the mask."""
     from .catalog import PipelineFITSCatalog
@@ -160,7 +174,10 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
         second = {}
     else:
         raise ValueError(f"columns={columns!r}: 'isophotal' or 'param'")
-    settings = extraction_settings(sextractor_kws, image.header, deblend=deblend, clean=clean)
+    from .extract import mask_setting
+    if mask_setting(mask) is not None and columns != 'param':
+        raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
+    settings = extraction_settings(sextractor_kws, image.header, deblend=deblend, clean=clean, mask=mask)
     settings.update(second)
     mask = getattr(image, 'mask_image', None)
     try:
@@ -175,6 +192,7 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
     cat.data = tab
     cat.deblend = settings.get('deblend')
     cat.clean = settings.get('clean')
+    cat.mask = settings.get('mask')
     cat.header = dict(image.header or {})
     cat.header_comments = dict(image.header_comments or {})
     if image.ismapped:
@@ -185,12 +203,13 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
 
 def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir='/tmp',
                    use_weightmap=True, sextractor_kws=None, catalog=False, columns='isophotal', deblend=False,
-                   clean=False):
+                   clean=False, mask=None):
     """Produce the requested check-images as FITSImage objects, written next to
     the image when it is mapped (``zuds/sextractor.py:110-150``).  The returned
     list starts with the catalog slot: ``None``, or with ``catalog=True`` (or when ``segm`` is among the
     check-images) the ``PipelineFITSCatalog`` of the image; ``columns='param'``: with the wide table; ``deblend``: with
-    multi-threshold deblending, ``clean``: with the CLEAN pass (``Engine.extract``)."""
+    multi-threshold deblending, ``clean``: with the CLEAN pass, ``mask='blank' | 'correct'`` (needs ``columns='param'``):
+    with the masked second pass (``Engine.extract``)."""
     from .engine import get_engine
     from .image import FITSImage
     call = prepare_sextractor(image, None, checkimage_type=checkimage_type,
@@ -208,7 +227,7 @@ def run_sextractor(image, checkimage_type=None, catalog_type='FITS_LDAC', tmpdir
     planes = {'bkg': bkg, 'rms': rms, 'bkgsub': sub}
     result = [None]
     if extracting:
-        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws, columns, deblend, clean)
+        result[0], planes['segm'] = _extract(image, call, sub, sextractor_kws, columns, deblend, clean, mask)
     for t, name in zip(call['types'], call['outnames']):
         product = FITSImage()
         product.basename = os.path.basename(name)

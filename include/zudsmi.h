@@ -288,6 +288,58 @@ int zm_aperture_photometry_dev(zm_ctx* ctx, const float* img, const float* rms,
                                const double* x, const double* y, double radius,
                                double* out_flux, double* out_err, int32_t* out_flags);
 
+/* ---- photometric calibration (csrc/photcal.hip; DESIGN.md "Photometric calibration") ---- */
+/* zm_growth: curves of growth with a local sky, one wave per star.  x, y: 0-based positions; radii: naper (1 .. 8)
+ * ascending aperture radii in pixels, HOST memory in both forms; the sky annulus is the pixels whose centres lie at
+ * r_in <= d < r_out (r_out <= ZM_GROWTH_ROUT_MAX), clipped to the frame; a pixel is usable when it is finite and
+ * (mask & bad_bits) == 0.  Sky: exact median of the usable float32 values (even count: mean of the two middle values in
+ * double), sky_sigma = 1.4826 x the exact median of |v - sky|; values with |v - sky| > kappa x sky_sigma are dropped
+ * and the two are taken again, until nothing is dropped or maxiter times.  nsky: the survivors; none: sky and
+ * sky_sigma NaN, every flux and err NaN.  Sums run over the bounding box of the largest radius, clipped as
+ * zm_aperture_photometry clips it: flux[s * naper + k] = sum((img - sky) frac_k) in fp64, err = sqrt(sum(rms^2
+ * frac_k)), or sqrt(sum(frac_k)) x sky_sigma when rms is NULL.  An rms value that is not finite (NaN or +-inf) makes NaN
+ * every err whose circle its pixel touches.  A pixel "touches" radius r when its nearest point to
+ * the centre lies nearer than r; a pixel that does not touch contributes nothing, one whose farthest corner lies
+ * within r counts whole.  flags: ZM_GROWTH_* below.  A position that is not finite: every output NaN, nsky 0, flags
+ * ZM_GROWTH_BADPOS.  saturate <= 0: no saturation test.  nstar == 0: returns at once, writes nothing.
+ * The host form stages the planes as zm_aperture_photometry does; the _dev form only enqueues on the stream. */
+#define ZM_GROWTH_NAPER_MAX 8
+#define ZM_GROWTH_ROUT_MAX 20.0
+#define ZM_GROWTH_BAD 1         /* a pixel with mask & bad_bits touches the largest aperture */
+#define ZM_GROWTH_SATURATED 2   /* a pixel >= saturate touches the largest aperture */
+#define ZM_GROWTH_NONFINITE 4   /* a non-finite pixel touches the largest aperture; every flux whose circle it touches is NaN */
+#define ZM_GROWTH_BOXCLIP 8     /* the box of the largest aperture was clipped by the frame */
+#define ZM_GROWTH_ANNCLIP 16    /* the annulus was clipped by the frame */
+#define ZM_GROWTH_FEWSKY 32     /* nsky < nsky_min (the fluxes are still reported) */
+#define ZM_GROWTH_BADPOS 64     /* the position is not finite */
+int zm_growth(zm_ctx* ctx, const float* img, const float* rms, const int32_t* mask, int32_t bad_bits,
+              float saturate, int nx, int ny, int nstar, const double* x, const double* y, int naper,
+              const double* radii, double r_in, double r_out, double kappa, int maxiter, int nsky_min,
+              double* out_flux, double* out_err, double* out_sky, double* out_sky_sigma, int32_t* out_nsky,
+              int32_t* out_flags);
+int zm_growth_dev(zm_ctx* ctx, const float* img, const float* rms, const int32_t* mask, int32_t bad_bits,
+                  float saturate, int nx, int ny, int nstar, const double* x, const double* y, int naper,
+                  const double* radii, double r_in, double r_out, double kappa, int maxiter, int nsky_min,
+                  double* out_flux, double* out_err, double* out_sky, double* out_sky_sigma, int32_t* out_nsky,
+                  int32_t* out_flags);
+/* zm_clipped_median: a clipped median per column, one workgroup per column.  values: n rows of ncol doubles, row
+ * stride `stride` elements (>= ncol); an entry that is not finite is not used.  The same iteration as the sky of
+ * zm_growth (median, 1.4826 x MAD, strict drop; maxiter 0: the plain median and MAD).  out[4 * c ..] = {median, sigma,
+ * n_used, n_valid}; n_valid 0 (or nothing left): median and sigma NaN.  n <= ZM_CLIPMED_NMAX: the column lies in LDS. */
+#define ZM_CLIPMED_NMAX 16384
+int zm_clipped_median(zm_ctx* ctx, const double* values, int n, int ncol, int64_t stride, double kappa, int maxiter,
+                      double* out);
+int zm_clipped_median_dev(zm_ctx* ctx, const double* values, int n, int ncol, int64_t stride, double kappa,
+                          int maxiter, double* out);
+/* zm_maglim_dev: the noise in an aperture over a lattice, for the limiting magnitude.  Centres (0-based) at
+ * step / 2 + i step in x and y, kept where the centre lies at least radius + 1 pixels from every edge of the frame
+ * (the frame spans -0.5 .. n - 0.5); sigma_ap = sqrt(sum(rms^2 frac)).  A point is used when no pixel of its aperture
+ * box has mask & bad_bits and every rms value in the box is finite and positive.  out3_dev (device) = {median sigma_ap
+ * of the used points (NaN: none), number used, number of lattice points}.  More than ZM_CLIPMED_NMAX lattice points:
+ * an error, take a coarser step.  mask may be NULL. */
+int zm_maglim_dev(zm_ctx* ctx, const float* rms, const int32_t* mask, int32_t bad_bits, int nx, int ny,
+                  double radius, int step, double* out3_dev);
+
 /* ---- device-pointer entry points (bench, multi-GPU, pipelines) ----------- */
 /* Same arithmetic as above on device-resident buffers; enqueue only. */
 typedef struct zm_dframe {

@@ -7,6 +7,7 @@ subtractions as one batch of launches on each of J lanes (``nightly.SubtractionP
 
 usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch B] [--batch FRAMES] [--nreg-side N]
                     [--detect [--stamps] [--deblend] [--clean [--clean-param X]] [--rb-model BASE [--rb-cut X]] [--associate [--stars F]]]
+                    [--maglim]
 
 * ``images.txt``: science image paths (``*sciimg.fits``; the mask is ``*mskimg.fits``; a
   ``.weight.fits`` sibling is required: 1 / rms^2, 0 on bad pixels).  The list is sharded over
@@ -28,6 +29,9 @@ reference's TooManyDetectionsError).  ``--deblend`` (needs ``--detect``): the ex
 ``DEBLEND_MINCONT`` 0.005; DESIGN.md "Deblending"): the tables carry ``PARENT_NUMBER`` and the headers say ``ZMDEBLND = T``.
 ``--clean`` (needs ``--detect``): the extraction ends with the CLEAN pass (``CLEAN_PARAM`` 1.0, or ``--clean-param X``;
 DESIGN.md "CLEAN"): the tables carry ``NMERGED`` and the headers say ``ZMCLEAN = T`` and ``ZMCLNPAR``.
+``--maglim``: every ``sub.*.fits`` gets a ``MAGLIM`` card, 5 sigma in an r = 3 px aperture, measured by the pool on the noise
+plane and mask in HBM (``SubtractionJob(maglim=True)`` -> ``DeviceSubtraction.maglim``) with ``MAGZP + APCOR4`` of the science
+header; a frame without those cards gets a warning and no card.
 ``--associate`` (needs ``--detect``): once the pool has drained, the night's
 in-memory tables go through ``zuds.associate`` (the job of ``nersc/makesources.py``; ``scripts/makesources.py`` does the
 same from the ``sub.*.cat`` files) and ``<images>.sources.txt`` / ``<images>.sources.det.txt`` are written next to the
@@ -151,6 +155,13 @@ def write_products(io, sci, ref, res):
     out = zuds.sub_name(sci['path'], ref['path'])
     hdr = dict(sci['header'])
     hdr.update(zuds.hotpants.info_cards(res['info']))    # KSUM00, NSTAMPS, ZMSTATUS, ZMUNSOLV, ZMRETRY
+    ml = res.get('maglim')
+    if ml is not None:
+        # --maglim: measured by the pool on the planes in HBM (DeviceSubtraction.maglim) with the science header's zero point
+        if np.isfinite(ml['maglim']):
+            hdr['MAGLIM'] = float(ml['maglim'])
+        else:
+            print(f'{os.path.basename(out)}: no usable aperture on the noise plane, MAGLIM is not written', flush=True)
     io.save(out, res['diff'], hdr)
     io.save(out.replace('.fits', '.rms.fits'), res['noise'], hdr)
     mh = dict(sci['header'])
@@ -203,6 +214,9 @@ def main(argv=None):
     ap.add_argument('--associate', action='store_true', help='with --detect: cluster the night\'s detections into sources '
                                                              'and write <images>.sources.txt / .sources.det.txt')
     ap.add_argument('--stars', help='with --associate: star catalogue (ra dec per line) for the 1.5 arcsec veto')
+    ap.add_argument('--maglim', action='store_true', help='write MAGLIM into sub.*.fits: 5 sigma in an r = 3 px aperture, from the '
+                                                          'subtraction\'s own noise plane and the MAGZP / APCOR4 of the science '
+                                                          'header (a frame without them: a warning, no card)')
     args = ap.parse_args(argv)
     if (args.associate or args.stars) and not (args.detect and (args.associate or not args.stars)):
         print('--associate needs --detect (and --stars needs --associate)', file=sys.stderr)
@@ -251,7 +265,7 @@ def main(argv=None):
     try:
         done = run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side,
                          detect=args.detect, stamps=args.stamps, rb_model=rb_model, rb_cut=args.rb_cut, tables=tables,
-                         deblend=args.deblend, clean=clean)
+                         deblend=args.deblend, clean=clean, maglim=args.maglim)
     finally:
         pool.close()
         ring.close()
@@ -277,7 +291,7 @@ def make_sources(tables, prefix, stars=None, engine=None):
 
 
 def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False, rb_model=None,
-              rb_cut=None, tables=None, deblend=False, clean=False):
+              rb_cut=None, tables=None, deblend=False, clean=False, maglim=False):
     """The images of this rank against one reference.  The files of batch b + 1 are read, sent and decoded by the
     ring (fitsring.FITSRing: reader threads, copy stream) while the pool subtracts batch b; the products of batch b
     are encoded on the device, copied back on a third stream and written by the ring's writer threads while
@@ -338,7 +352,8 @@ def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, dete
                     # the filter id as image.py reads it; a frame without the card and no --rb-cut fails here (ValueError)
                     rbkw = dict(rb_model=rb_model, rb_cut=rb_cut, fid=hdr.get('FID', hdr.get('FILTERID')))
                 job = nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
-                                             stamps=stamps, max_detections=MAX_DETS, deblend=deblend, clean=clean, **rbkw)
+                                             stamps=stamps, max_detections=MAX_DETS, deblend=deblend, clean=clean, maglim=maglim,
+                                             **rbkw)
             except Exception:
                 # (the reference's drivers: try / except per image, scripts/dosub.py:205-213)
                 traceback.print_exception(*sys.exc_info())

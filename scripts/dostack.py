@@ -14,6 +14,11 @@ output already exists is skipped, which is how an interrupted run resumes.
 
 refits the astrometry of the inputs and of the coadd against the FITS_LDAC star catalogue ``stars.cat``
 (``from_images(solve_astrometry=True)``; the reference's SCAMP step, ``zuds/coadd.py:120-123,219-223``).
+
+    dostack.py jobs.csv --photcal [--photref stars.cat]
+
+measures ``APCORk`` and ``MAGLIM`` on every coadd - with ``--photref``, a FITS_LDAC star catalogue with a ``MAG`` column,
+``MAGZP`` as well - and writes the cards into its header (``from_images(calibrate_photometry=True)``, photcal.py).
 """
 import argparse
 import os
@@ -45,7 +50,7 @@ def coadd_name(first, left, right):
     return os.path.join(os.path.dirname(first.local_path), stem + '.coadd.fits')
 
 
-def run_job(job, tmpdir, scamp_kws=None):
+def run_job(job, tmpdir, scamp_kws=None, photcal_kws=None):
     t0 = time.time()
     images = load_inputs(job['target'])
     outname = coadd_name(images[0], job['left'], job['right'])
@@ -57,7 +62,8 @@ def run_job(job, tmpdir, scamp_kws=None):
         stack = zuds.ScienceCoadd.from_images(images, outfile_name=outname,
                                               data_product=False, tmpdir=tmpdir,
                                               nthreads=zuds.get_nthreads(),
-                                              solve_astrometry=scamp_kws is not None, scamp_kws=scamp_kws)
+                                              solve_astrometry=scamp_kws is not None, scamp_kws=scamp_kws,
+                                              calibrate_photometry=photcal_kws is not None, photcal_kws=photcal_kws)
     except Exception as exc:        # one bad job must not end the night's run
         print(exc, [im.basename for im in images], flush=True)
         return None
@@ -79,7 +85,14 @@ def main(argv=None):
     ap.add_argument('--solve-astrometry', action='store_true', help='refit the astrometry of the inputs and of the coadd')
     ap.add_argument('--astref', help='FITS_LDAC star catalogue (ASTREF_CATALOG FILE, ASTREFCAT_NAME)')
     ap.add_argument('--distort-degrees', type=int, default=3, help='degree of the distortion polynomial (1, 2 or 3)')
+    ap.add_argument('--photcal', action='store_true', help='measure APCORk and MAGLIM (with --photref: MAGZP) on the coadd')
+    ap.add_argument('--photref', help='FITS_LDAC star catalogue with a MAG column (PHOTREF_NAME)')
     args = ap.parse_args(argv)
+    if args.photref and not args.photcal:
+        ap.error('--photref is only read with --photcal')
+    photcal_kws = None
+    if args.photcal:
+        photcal_kws = {'PHOTREF_NAME': args.photref} if args.photref else {}
     scamp_kws = None
     if args.solve_astrometry:
         if not args.astref:
@@ -89,7 +102,7 @@ def main(argv=None):
     share = zuds.get_my_share_of_work(args.jobs, reader=pd.read_csv)
     table = share if isinstance(share, pd.DataFrame) else pd.DataFrame(list(share))
     for _, row in table.iterrows():
-        run_job(row, args.tmpdir, scamp_kws)
+        run_job(row, args.tmpdir, scamp_kws, photcal_kws)
     return 0
 
 

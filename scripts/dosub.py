@@ -4,10 +4,13 @@
 
 usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns [--mask-type blank|correct]] [--deblend]
                                         [--clean [--clean-param X]]
-                                        [--rb-model BASE [--rb-cut X]]]
+                                        [--rb-model BASE [--rb-cut X]]] [--maglim]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
+With ``--maglim`` every subtraction gets a ``MAGLIM`` card measured on its own rms plane with the ``MAGZP`` and ``APCOR4``
+it copied from the science image (``write_maglim``: the median noise in r = 3 px apertures on a lattice, 5 sigma); a
+subtraction without a zero point is left without the card, with a warning.
 With ``--detect`` every subtraction also gets its detection catalog (``sub.*.cat``, FITS_LDAC) and its filtered
 detections (``PipelineFITSCatalog.from_image`` -> ``Detection.from_catalog``, dosub.py:109-131).
 With ``--param-columns`` (needs ``--detect``) the catalog holds every column of ``sextractor.param`` (``MAG_AUTO``,
@@ -85,7 +88,7 @@ def write_stamps(sub, detections, stamps, size=None):
 
 
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
-           rb_cut=None, deblend=False, clean=False, mask=None):
+           rb_cut=None, deblend=False, clean=False, mask=None, maglim=False):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -123,6 +126,10 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
     sub = subclass.from_images(sci, ref, data_product=False, tmpdir=tmpdir, refined=True)
     substop = time.time()
     print(f'sub: {substop - substart:.2f} sec to make {sub.basename}', flush=True)
+    if maglim:
+        # MAGLIM from the subtraction's own rms plane and the MAGZP / APCOR4 it copied from the science image; without a
+        # zero point the card is skipped with a warning
+        zuds.write_maglim(sub)
 
     detections = None
     if detect:
@@ -166,6 +173,7 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
 
 def main(argv):
     detect = '--detect' in argv
+    maglim = '--maglim' in argv
     stamps = '--stamps' in argv
     param_columns = '--param-columns' in argv
     if stamps and not detect:
@@ -221,7 +229,7 @@ def main(argv):
         return 2
     if rb_model:
         rb_model = zuds.load_model(rb_model)
-    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend', '--clean')]
+    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend', '--clean', '--maglim')]
     infile = args[0]
     refname = args[1]
     subclass = zuds.SingleEpochSubtraction
@@ -230,7 +238,7 @@ def main(argv):
     for fn in imgs:
         try:
             do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
-                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask)
+                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask, maglim=maglim)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

@@ -3,6 +3,7 @@
 database-free.
 
 usage: makeref.py dirs.txt min_date max_date version [--solve-astrometry --astref FILE [--distort-degrees N]]
+                  [--photcal [--photref stars.cat]]
 
 ``dirs.txt`` lists directories; each is searched for ``ztf*sciimg.fits`` (masks as
 ``*mskimg.fits`` beside them).  The selection is the reference's
@@ -15,6 +16,8 @@ is written into the directory by ``ReferenceImage.from_images`` - one ``zm_coadd
 the reference ran SWarp twice.  A directory whose reference exists is skipped (resume by name).
 The reference's catalog / archive / database steps that follow are out of scope here.
 
+``--photcal``: measure ``APCORk`` and ``MAGLIM`` on the reference (with ``--photref FILE``, a FITS_LDAC star catalogue with
+a ``MAG`` column, ``MAGZP`` as well) and write the cards into its header (``from_images(calibrate_photometry=True)``).
 ``--solve-astrometry --astref FILE``: refit the astrometry of the inputs and of the reference against the FITS_LDAC
 star catalogue FILE (``from_images(solve_astrometry=True)``; ``--distort-degrees`` 1, 2 or 3, default 3).
 """
@@ -74,7 +77,7 @@ def select(directory, min_date, max_date):
     return sorted(ok, key=lambda i: float(i.header['MAGLIM']), reverse=True)[:MAX_FRAMES]
 
 
-def make_one(directory, min_date, max_date, version, tmpdir='./tmp', scamp_kws=None):
+def make_one(directory, min_date, max_date, version, tmpdir='./tmp', scamp_kws=None, photcal_kws=None):
     t_start = time.time()
     top = select(directory, min_date, max_date)
     if len(top) == 0:
@@ -94,7 +97,8 @@ def make_one(directory, min_date, max_date, version, tmpdir='./tmp', scamp_kws=N
     try:
         coadd = zuds.ReferenceImage.from_images(top, coaddname, data_product=True,
                                                 nthreads=zuds.get_nthreads(), tmpdir=tmpdir,
-                                                solve_astrometry=scamp_kws is not None, scamp_kws=scamp_kws)
+                                                solve_astrometry=scamp_kws is not None, scamp_kws=scamp_kws,
+                                                calibrate_photometry=photcal_kws is not None, photcal_kws=photcal_kws)
         coadd.version = version
     except TypeError as e:
         print(e, [t.basename for t in top], coaddname)
@@ -135,8 +139,27 @@ def astrometry_options(argv):
     return rest, {'ASTREF_CATALOG': 'FILE', 'ASTREFCAT_NAME': astref, 'DISTORT_DEGREES': degree}
 
 
+def photcal_options(argv):
+    """(argv without --photcal / --photref FILE, photcal_kws or None)."""
+    on, photref, rest = False, None, []
+    it = iter(argv)
+    for a in it:
+        if a == '--photcal':
+            on = True
+        elif a == '--photref':
+            photref = next(it, None)
+            if photref is None or photref.startswith('--'):
+                sys.exit('--photref needs a value')
+        else:
+            rest.append(a)
+    if photref is not None and not on:
+        sys.exit('--photref is only read with --photcal')
+    return rest, (({'PHOTREF_NAME': photref} if photref else {}) if on else None)
+
+
 def main(argv=None):
-    argv, scamp_kws = astrometry_options(list(sys.argv[1:] if argv is None else argv))
+    argv, photcal_kws = photcal_options(list(sys.argv[1:] if argv is None else argv))
+    argv, scamp_kws = astrometry_options(argv)
     if len(argv) != 4:
         sys.exit(__doc__)
     infile, version = argv[0], argv[3]
@@ -144,7 +167,7 @@ def main(argv=None):
     zuds.init_db()
     made = []
     for d in zuds.get_my_share_of_work(infile):
-        coadd = make_one(str(d), min_date, max_date, version, scamp_kws=scamp_kws)
+        coadd = make_one(str(d), min_date, max_date, version, scamp_kws=scamp_kws, photcal_kws=photcal_kws)
         if coadd is not None:
             made.append(coadd.local_path)
     return made

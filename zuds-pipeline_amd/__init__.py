@@ -36,7 +36,8 @@ from .source import *
 from .lightcurve import *
 from .alert import *
 from .scamp import *
-from . import synth, fits, scamp, lightcurve
+from .photcal import *
+from . import synth, fits, scamp, lightcurve, photcal
 
 # same DB-free entry points as the reference
 def init_db(*args, **kwargs):

@@ -195,7 +195,10 @@ EXTRACT_DEBLEND = 2                                    # zm_extract_deblend stat
 EXTRACT_CLEAN = 4                                      # zm_extract_clean status bit (ZM_EXTRACT_CLEAN)
 MASK_BLANK, MASK_CORRECT = 1, 2                        # zm_mask_params.type (ZM_MASK_*)
 AUTO_CROWDED = 8                                       # flags_auto bit of the masked pass (ZM_AUTO_CROWDED)
-HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4          # zm_hp_info.status bits (include/zudsmi.h)
+GROWTH_NAPER_MAX, GROWTH_ROUT_MAX, CLIPMED_NMAX = 8, 20.0, 16384      # ZM_GROWTH_NAPER_MAX, ZM_GROWTH_ROUT_MAX, ZM_CLIPMED_NMAX
+GROWTH_BAD, GROWTH_SATURATED, GROWTH_NONFINITE, GROWTH_BOXCLIP, GROWTH_ANNCLIP, GROWTH_FEWSKY, GROWTH_BADPOS = \
+    1, 2, 4, 8, 16, 32, 64                             # flags of zm_growth (ZM_GROWTH_*)
+HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4         # zm_hp_info.status bits (include/zudsmi.h)
 
 
 _P = C.c_void_p
@@ -296,6 +299,13 @@ _SIGS = {
                                          C.c_double, _P, _P, _P]),
     'zm_aperture_photometry_dev': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P,
                                              C.c_double, _P, _P, _P]),
+    'zm_growth': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P,
+                            C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    'zm_growth_dev': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P,
+                                C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    'zm_clipped_median': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, _P]),
+    'zm_clipped_median_dev': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, _P]),
+    'zm_maglim_dev': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_double, C.c_int, _P]),
     'zm_extract_params_default': (None, [C.POINTER(zm_extract_params)]),
     'zm_extract_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
                                  C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

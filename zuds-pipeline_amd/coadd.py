@@ -20,13 +20,18 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
                        sci_swarp_kws=None, mask_swarp_kws=None, calculate_seeing=True,
                        addbkg=True, enforce_partition=True, solve_astrometry=False,
                        swarp_zp_key='MAGZP', scamp_kws=None, set_date=True,
-                       outfile_name=None, nthreads=None, **ignored):
+                       outfile_name=None, nthreads=None, calibrate_photometry=False, photcal_kws=None,
+                       **ignored):
     """Make a coadd from a bunch of input images (``zuds/coadd.py:25-236``).
 
     ``outfile_name`` and ``nthreads`` are the keyword spellings the driver
     scripts use (``scripts/dostack.py:60-63``, ``scripts/makeref.py:87``); other
     unknown keywords are ignored like the reference's SWarp pass-through
-    would."""
+    would.
+
+    ``calibrate_photometry``: measure ``APCORk``, ``MAGLIM`` and, with ``PHOTREF_NAME`` in ``photcal_kws``, ``MAGZP`` on
+    the coadd and write the cards into its header (``photcal.calibrate_photometry``; off by default: the reference
+    inherits these cards from its inputs and a coadd has none)."""
     from . import fits as _fits
     from .engine import coadd_params, get_engine
     from .mask import MaskImage
@@ -87,6 +92,8 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
         coadd.input_images = inputs.tolist()
         if solve_astrometry:
             _solve_coadd(coadd, scamp_kws, tmpdir)
+        if calibrate_photometry:
+            _calibrate_coadd(coadd, photcal_kws)
         return coadd
 
     # one fused device pass: science frames and their masks share the lattice
@@ -145,9 +152,17 @@ def _coadd_from_images(cls, images, outname=None, data_product=False, tmpdir='/t
                 coadd.header['SEEING'] = float(np.median(see))
                 coadd.header_comments['SEEING'] = 'Median SEEING of the coadd inputs (pixels)'
                 coadd.save()
+    if calibrate_photometry:
+        _calibrate_coadd(coadd, photcal_kws)
     if data_product:
         warnings.warn('data_product=True: archiving is not part of this package')
     return coadd
+
+
+def _calibrate_coadd(coadd, photcal_kws):
+    """The photometric cards of a finished coadd, measured on its own pixels and saved with it (photcal.py)."""
+    from .photcal import calibrate_photometry
+    coadd.photcal_info = calibrate_photometry([coadd], photcal_kws=photcal_kws, inplace=True)[0]
 
 
 def _solve_coadd(coadd, scamp_kws, tmpdir):

@@ -259,6 +259,17 @@ class DeviceSubtraction(object):
                                                   wcs=self.wsci if wcs is None else wcs, segm=segm.data_ptr(), **kw)
         return tab, nfound, segm
 
+    def maglim(self, zp, nsigma=5.0, step=32):
+        """The limiting magnitude of the resident difference image from its noise plane and mask (``photcal.
+        limiting_magnitude`` on ``noise`` / ``submask``: ``zm_maglim_dev``, three doubles cross PCIe).  ``zp``: the zero
+        point of r = 3 px aperture fluxes, ``MAGZP + APCOR4`` of the science image.  Returns the dict of
+        ``limiting_magnitude``; its ``maglim`` is what ``MAGLIM`` of ``sub.*.fits`` should carry."""
+        from .photcal import limiting_magnitude
+        self.engine.set_stream(self.stream.cuda_stream)
+        with self.torch.cuda.stream(self.stream):
+            return limiting_magnitude((self.noise, self.submask), zp, nsigma=nsigma, step=step, bad_bits=self.BAD_SUM,
+                                      engine=self.engine)
+
     def candidates(self, seeing, wcs=None, max_objects=None, rb_model=None, sci=None, ref=None, fid=None, rb_cut=None,
                    sci_flxscale=1.0, deblend=False, clean=False, mask=None, **extract_params):
         """The filtered detection table of the resident difference image: ``extract``, the ``kill_flagged`` rule of

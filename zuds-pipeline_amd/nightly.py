@@ -21,13 +21,14 @@ so that one lane's throughput kernels run beside another lane's fit.  Same produ
 """
 import os
 import threading
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 from . import _lib
 from ._lib import check
-from .constants import APERTURE_RADIUS
+from .constants import APER_KEY, APERTURE_RADIUS
 from .engine import Engine
 
 __all__ = ['SubtractionPool', 'SubtractionJob']
@@ -62,11 +63,14 @@ class SubtractionJob(object):
     result then carries ``clean``, the settings used.
     ``columns`` (with ``detect``): 'isophotal' or 'param', the table of ``DeviceSubtraction.candidates``.
     ``mask`` (with ``detect`` and ``columns='param'``): None, 'blank' or 'correct', the masked second pass of
-    ``DeviceSubtraction.candidates``; the result then carries ``mask``."""
+    ``DeviceSubtraction.candidates``; the result then carries ``mask``.
+    ``maglim``: the result also carries ``maglim``, the dict of ``DeviceSubtraction.maglim`` on the resident noise plane
+    and mask with the zero point ``MAGZP + APCOR4`` of ``sci['header']``; a frame without those cards gets a warning and
+    no ``maglim``.  The three doubles cross to the host, so this waits for the chain."""
 
     def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
                  max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False, clean=False,
-                 columns='isophotal', mask=None):
+                 columns='isophotal', mask=None, maglim=False):
         if stamps and not detect:
             raise ValueError('stamps needs detect')
         if rb_model is not None:
@@ -94,6 +98,7 @@ class SubtractionJob(object):
         self.sci, self.ref, self.radec = sci, ref, radec
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag
         self.detect, self.stamps, self.max_detections = bool(detect), bool(stamps), int(max_detections)
+        self.maglim = bool(maglim)
 
 
 class _Worker(object):
@@ -174,6 +179,12 @@ def _collect(w, ch, job, info, diff, noise, mask, keep):
         out['phot'] = dict(x=x, y=y, _pending=(res_h, flg_h, res, flg, pos))
     if getattr(job, 'detect', False):
         _detect(ch, job, out)
+    if getattr(job, 'maglim', False):
+        hdr = sci.get('header') or {}
+        if 'MAGZP' in hdr and APER_KEY in hdr:
+            out['maglim'] = ch.maglim(float(hdr['MAGZP']) + float(hdr[APER_KEY]))
+        else:
+            warnings.warn(f'{job.tag}: the science header has no MAGZP / {APER_KEY} card: MAGLIM is not measured')
     if keep:
         with torch.cuda.stream(w.stream):
             out['diff'], out['noise'], out['mask'] = diff.clone(), noise.clone(), mask.clone()

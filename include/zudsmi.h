@@ -965,6 +965,85 @@ int zm_forced_photometry_batch_dev(zm_ctx* ctx, int nimg, const zm_lc_image* ima
                                    const double* dec_dev, double radius, double* x_dev, double* y_dev, double* flux_dev,
                                    double* err_dev, int32_t* flags_dev);
 
+/* ---- PSF photometry: star model and batched fits (csrc/psf.hip; DESIGN.md "PSF photometry") ---- */
+/* Taps: Lanczos-3, separable, fp64: offsets k = -2 .. 3 from the floor sample, t_k ~ sinc(d - k) sinc((d - k) / 3), each
+ * 6-vector scaled to unit sum; at d == 0 exactly the vector is a delta and its footprint on that axis the single sample.
+ *
+ * zm_psf_build: the model of an image from nstar stars - x, y (0-based centroids), sky (local sky) and norm (flux in the
+ * reference aperture above that sky: zm_growth's outputs).  The model is (2 half + 1)^2 doubles at the image's own
+ * sampling, row j + half, column i + half for the offset (i, j) from the centre; 1 <= half <= ZM_PSF_HALF_MAX.
+ * Cutout entry (j, i) of star s: the Lanczos-3 interpolation of (img - sky_s) / norm_s at (x + i, y + j).  An entry is NaN
+ * when any tap of its footprint lies outside the frame, on a pixel that is not finite, or on one with mask & bad_bits; a
+ * whole row is NaN when x, y, sky or norm is not finite or norm <= 0.  Model: the clipped median over the stars of
+ * every entry (zm_clipped_median_dev with kappa / maxiter: NaN entries are not used); then 0 where i^2 + j^2 >
+ * norm_radius^2 (squares compared), where n_used < min_stars_pixel, or where no star gave a value; then scaled to unit
+ * sum (fp64, fixed order).  A sum that is not positive and finite: every entry NaN.  out_n_used[(2 half + 1)^2]: the
+ * stars that entered the median of every entry, exact.  out_cutouts: NULL, or nstar rows of cutout_stride (>= (2 half +
+ * 1)^2) doubles.  nstar <= ZM_CLIPMED_NMAX, more is an error; nstar == 0: returns at once, writes nothing.
+ * The host form stages the planes as zm_aperture_photometry does; the _dev form (every array device memory) only
+ * enqueues on the stream. */
+#define ZM_PSF_HALF_MAX 15
+int zm_psf_build(zm_ctx* ctx, const float* img, const int32_t* mask, int32_t bad_bits, int nx, int ny, int nstar,
+                 const double* x, const double* y, const double* sky, const double* norm, int half, double norm_radius,
+                 double kappa, int maxiter, int min_stars_pixel, double* out_model, int32_t* out_n_used,
+                 double* out_cutouts, int64_t cutout_stride);
+int zm_psf_build_dev(zm_ctx* ctx, const float* img, const int32_t* mask, int32_t bad_bits, int nx, int ny, int nstar,
+                     const double* x, const double* y, const double* sky, const double* norm, int half,
+                     double norm_radius, double kappa, int maxiter, int min_stars_pixel, double* out_model,
+                     int32_t* out_n_used, double* out_cutouts, int64_t cutout_stride);
+/* zm_psf_photometry: a linear fit of the model at npos given 0-based positions, one wave per position.  ix = floor(x +
+ * 0.5), fx = x - ix in [-0.5, 0.5), the same in y.  Pixels: (ix + i, iy + j) with (i - fx)^2 + (j - fy)^2 <= R^2 (centre
+ * rule, squares compared as plain IEEE operations), clipped to the frame; R = fit_radius, and R + 3.5 <= half is
+ * required (an error otherwise).  Profile: P_ij = the model interpolated at (i - fx, j - fy) with the taps above (the model
+ * is 0 outside its grid).  A pixel is used when its value is finite, (mask & bad_bits) == 0 and, with an rms plane, its rms
+ * is finite and positive; weight w = 1 / rms^2, or 1 when rms is NULL.  fit_sky == 0: flux = sum(w P d) / sum(w P^2), err =
+ * 1 / sqrt(sum(w P^2)), sky = 0.  fit_sky != 0: the 2 x 2 weighted least squares for {flux, sky}, err from the inverse
+ * normal matrix (solved about the weighted mean of P).  rms NULL: err is scaled by sqrt(chi2 / (npix - nparam)), NaN when
+ * npix <= nparam.  chi2 = sum(w (d - flux P - sky)^2), npix = pixels used (exact), cover = sum(P) over the used pixels /
+ * sum(P) over the pixels of the circle inside the frame.  flags: ZM_PSF_* below, exact.  With ZM_PSF_SINGULAR or
+ * ZM_PSF_BADPOS every float output is NaN.  All sums are fp64 in a fixed order: the same bits on every run.
+ * ZM_PSF_SINGULAR is exact where a circle holds fewer usable pixels than parameters; on a circle that is only nearly rank
+ * deficient (two parameters on a few pixels of nearly equal profile, as R = 1 with a sky term) the decision is this
+ * kernel's Sxx > 0 and is not pinned: another solver may call such a fit singular, or return very different numbers.
+ * npos == 0: returns at once, writes nothing.  Host form: planes staged as zm_aperture_photometry does; _dev: enqueues. */
+#define ZM_PSF_BAD 1          /* a pixel of the circle was left out for its mask */
+#define ZM_PSF_NONFINITE 2    /* a pixel of the circle was left out because its value is not finite */
+#define ZM_PSF_BADRMS 4       /* a pixel of the circle was left out for its rms (not finite, or not positive) */
+#define ZM_PSF_CLIPPED 8      /* the frame cut the circle */
+#define ZM_PSF_LOWCOVER 16    /* cover < 0.5 */
+#define ZM_PSF_SINGULAR 32    /* fewer pixels left than parameters, or the determinant is not positive */
+#define ZM_PSF_BADPOS 64      /* the position is not finite (npix 0) */
+int zm_psf_photometry(zm_ctx* ctx, const float* img, const float* rms, const int32_t* mask, int32_t bad_bits, int nx,
+                      int ny, int npos, const double* x, const double* y, const double* model, int half,
+                      double fit_radius, int fit_sky, double* out_flux, double* out_err, double* out_chi2,
+                      double* out_sky, double* out_cover, int32_t* out_npix, int32_t* out_flags);
+int zm_psf_photometry_dev(zm_ctx* ctx, const float* img, const float* rms, const int32_t* mask, int32_t bad_bits, int nx,
+                          int ny, int npos, const double* x, const double* y, const double* model, int half,
+                          double fit_radius, int fit_sky, double* out_flux, double* out_err, double* out_chi2,
+                          double* out_sky, double* out_cover, int32_t* out_npix, int32_t* out_flags);
+
+typedef struct zm_psf_image {   /* zm_lc_image, then the model of the image */
+    const float* img;       /* device, ny x nx */
+    const float* rms;       /* device or NULL */
+    const int32_t* mask;    /* device or NULL */
+    zm_wcs wcs;
+    int32_t nx, ny;
+    const double* model;    /* device, (2 half + 1)^2 */
+    int32_t half;
+    int32_t pad_;
+} zm_psf_image;
+
+/* The fits of every pair of a join in one launch, one wave per pair: zm_forced_photometry_batch_dev with
+ * zm_psf_photometry_dev in place of the aperture sum.  At the positions it returns (x, y) every other output is bit for bit
+ * what zm_psf_photometry_dev returns there with the image's planes and model.  rms / mask may be NULL per image; sizes
+ * and half may differ from image to image (fit_radius + 3.5 <= half of every image).  A src_idx entry outside 0 .. nsrc - 1
+ * gives NaN positions and ZM_PSF_BADPOS.  Enqueued on the context's stream, nothing waited for. */
+int zm_psf_photometry_batch_dev(zm_ctx* ctx, int nimg, const zm_psf_image* images, const int64_t* offsets_dev,
+                                const int32_t* src_idx_dev, int64_t npairs, int nsrc, const double* ra_dev,
+                                const double* dec_dev, int32_t bad_bits, double fit_radius, int fit_sky, double* x_dev,
+                                double* y_dev, double* flux_dev, double* err_dev, double* chi2_dev, double* sky_dev,
+                                double* cover_dev, int32_t* npix_dev, int32_t* flags_dev);
+
 /* ---- alert packets: cone searches against a catalogue that stays in HBM -------- */
 /* The cone searches of the reference's xmatch() (zuds/crossmatch.py: the three nearest PS1 and LegacySurvey rows within
  * 30 arcsec, every ZTF alert, milliquas and TNS row within 1.5 arcsec) against local tables (csrc/skyindex.hip; DESIGN.md,

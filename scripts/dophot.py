@@ -2,7 +2,7 @@
 """Forced photometry of known sources on a list of subtractions: the job of the reference's ``scripts/dophot.py``,
 database-free.
 
-usage: dophot.py subs.txt out.csv --sources sources.txt [--done prior.csv] [--batch N]
+usage: dophot.py subs.txt out.csv --sources sources.txt [--done prior.csv] [--batch N] [--psf]
 
 * ``subs.txt``: one subtraction per line, ``path [image id]`` (the id defaults to the file's name).  ``X.rms.fits`` and
   ``X.mask.fits`` are looked for beside ``X.fits``; a triple that is incomplete is skipped with the reference's message.
@@ -10,6 +10,10 @@ usage: dophot.py subs.txt out.csv --sources sources.txt [--done prior.csv] [--ba
 * ``--done prior.csv``: an earlier output of this script: (source, image) pairs it holds are left out - the reference's
   outer join against the ``forcedphotometry`` table.
 * ``--batch N``: triples brought into HBM, joined and photometered per call (default 16).
+* ``--psf``: PSF fits in place of the aperture sums ("PSF photometry"): the model ``X.psf.fits`` that
+  ``dosub.py --psf`` wrote beside ``X.fits`` is fitted at every source (``method='psf'``: no sky term on a difference
+  image), ``flags`` are those of the fit and ``zp = MAGZP + PSFCOR``.  A subtraction without a model is skipped with a
+  warning.  The columns stay the reference's; write a PSF run to a file of its own.
 
 For every subtraction the reference asks the database which sources lie inside ``wcs.calc_footprint()`` and are not yet
 photometered, then runs ``raw_aperture_photometry`` there.  Here ``N`` triples at a time are read straight into HBM
@@ -57,9 +61,16 @@ def main(argv=None):
     ap.add_argument('--sources', required=True, help='sources table (id ra dec ...)')
     ap.add_argument('--done', help='an earlier output: pairs it holds are left out')
     ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--psf', action='store_true', help='PSF fits with the model beside each subtraction')
     args = ap.parse_args(argv)
     start = time.time()
     subs = read_subs(args.infile)
+    if args.psf:
+        for fn, _ in subs:
+            if not os.path.exists(fn.replace('.fits', '.psf.fits')):
+                print(f'phot: {fn} has no {os.path.basename(fn).replace(".fits", ".psf.fits")} beside it, skipped '
+                      f'(dosub.py --psf writes it)', flush=True)
+        subs = [(fn, imgid) for fn, imgid in subs if os.path.exists(fn.replace('.fits', '.psf.fits'))]
     sources = zuds.read_sources_table(args.sources)
     ids = [s.id for s in sources]
     ra = np.array([s.ra for s in sources], dtype=np.float64)
@@ -83,11 +94,16 @@ def main(argv=None):
         for k in range(len(batch)):
             (img, hdr), (rms, _), (mask, _) = planes[3 * k:3 * k + 3]
             images.append(dict(img=img, rms=rms, mask=mask, wcs=zuds.WCS.from_header(hdr)))
+            if args.psf:
+                images[-1]['psf'] = zuds.PSFModel.from_file(batch[k][0].replace('.fits', '.psf.fits'))
+                hdr = dict(hdr)
+                hdr.setdefault('PSFCOR', images[-1]['psf'].cards.get('PSFCOR'))
             headers.append(hdr)
         done = [(k, s) for k, (_, imgid) in enumerate(batch) for s in prior.get(str(imgid), ())]
         tstart = time.time()
-        table = zuds.forced_photometry_batch(images, ra, dec, done=done or None, engine=io.engine)
-        rows = zuds.photometry_rows(table, headers, ra, dec, source_ids=ids, image_ids=[imgid for _, imgid in batch])
+        method = dict(method='psf') if args.psf else {}
+        table = zuds.forced_photometry_batch(images, ra, dec, done=done or None, engine=io.engine, **method)
+        rows = zuds.photometry_rows(table, headers, ra, dec, source_ids=ids, image_ids=[imgid for _, imgid in batch], **method)
         zuds.write_phot_csv(args.outfile, rows, append=True)
         nrows += len(rows)
         for k, (fn, _) in enumerate(batch):

@@ -4,13 +4,18 @@
 
 usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns [--mask-type blank|correct]] [--deblend]
                                         [--clean [--clean-param X]]
-                                        [--rb-model BASE [--rb-cut X]]] [--maglim]
+                                        [--rb-model BASE [--rb-cut X]]] [--maglim] [--psf [--psfref stars.cat]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
 With ``--maglim`` every subtraction gets a ``MAGLIM`` card measured on its own rms plane with the ``MAGZP`` and ``APCOR4``
 it copied from the science image (``write_maglim``: the median noise in r = 3 px apertures on a lattice, 5 sigma); a
 subtraction without a zero point is left without the card, with a warning.
+With ``--psf`` the PSF model of every science image is built from its own stars, or with ``--psfref stars.cat`` from the
+stars of a FITS_LDAC catalogue (``CalibratedImage.build_psf``; DESIGN.md, "PSF photometry"), and written as
+``<sci>.psf.fits`` and - the difference image has the science frame's PSF - copied as ``sub.*.psf.fits``; its cards
+(``PSFCOR``, ``PSFCORUN``, ``PSFNSTAR``, ``PSFHALF``, ``PSFFITR``, ``PSFFWHM``, ``ZMPSF``) go into the subtraction's header.
+``dophot.py --psf`` reads the model beside each subtraction.  Without ``--psf`` nothing changes.
 With ``--detect`` every subtraction also gets its detection catalog (``sub.*.cat``, FITS_LDAC) and its filtered
 detections (``PipelineFITSCatalog.from_image`` -> ``Detection.from_catalog``, dosub.py:109-131).
 With ``--param-columns`` (needs ``--detect``) the catalog holds every column of ``sextractor.param`` (``MAG_AUTO``,
@@ -88,7 +93,7 @@ def write_stamps(sub, detections, stamps, size=None):
 
 
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
-           rb_cut=None, deblend=False, clean=False, mask=None, maglim=False):
+           rb_cut=None, deblend=False, clean=False, mask=None, maglim=False, psf=False, psfref=None):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -130,6 +135,22 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
         # MAGLIM from the subtraction's own rms plane and the MAGZP / APCOR4 it copied from the science image; without a
         # zero point the card is skipped with a warning
         zuds.write_maglim(sub)
+    if psf:
+        # the model of the science image (with -c t -n i the difference image has its PSF), copied beside the subtraction
+        pstart = time.time()
+        model = sci.build_psf(stars=psfref)['psf']
+        model.save(sci.local_path.replace('.fits', '.psf.fits'))
+        model.save(sub.local_path.replace('.fits', '.psf.fits'))
+        sub.psf_model = model
+        if sub.header_comments is None:
+            sub.header_comments = {}
+        for key, value in model.cards.items():
+            sub.header[key] = value
+            sub.header_comments[key] = zuds.psf.CARD_COMMENTS.get(key, '')
+        if sub.ismapped:
+            sub.save()
+        print(f'psf: {time.time() - pstart:.2f} sec to model {sci.basename} ({model.cards["PSFNSTAR"]} stars, '
+              f'PSFCOR {model.cards["PSFCOR"]:.4f})', flush=True)
 
     detections = None
     if detect:
@@ -174,6 +195,7 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
 def main(argv):
     detect = '--detect' in argv
     maglim = '--maglim' in argv
+    psf = '--psf' in argv
     stamps = '--stamps' in argv
     param_columns = '--param-columns' in argv
     if stamps and not detect:
@@ -194,8 +216,8 @@ def main(argv):
         print('--clean-param needs --clean', file=sys.stderr)
         return 2
     argv = list(argv)
-    rb_model = rb_cut = mask = None
-    for flag in ('--rb-model', '--rb-cut', '--clean-param', '--mask-type'):
+    rb_model = rb_cut = mask = psfref = None
+    for flag in ('--rb-model', '--rb-cut', '--clean-param', '--mask-type', '--psfref'):
         if flag in argv:
             k = argv.index(flag)
             if k + 1 >= len(argv):
@@ -205,6 +227,8 @@ def main(argv):
             del argv[k:k + 2]
             if flag == '--rb-model':
                 rb_model = value
+            elif flag == '--psfref':
+                psfref = value
             elif flag == '--mask-type':
                 if value not in ('blank', 'correct'):
                     print(f'--mask-type: {value!r} is neither blank nor correct', file=sys.stderr)
@@ -218,6 +242,9 @@ def main(argv):
                     return 2
             else:
                 rb_cut = float(value)
+    if psfref is not None and not psf:
+        print('--psfref needs --psf', file=sys.stderr)
+        return 2
     if mask is not None and not param_columns:
         print('--mask-type needs --param-columns', file=sys.stderr)
         return 2
@@ -229,7 +256,7 @@ def main(argv):
         return 2
     if rb_model:
         rb_model = zuds.load_model(rb_model)
-    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend', '--clean', '--maglim')]
+    args = [a for a in argv if a not in ('--detect', '--stamps', '--param-columns', '--deblend', '--clean', '--maglim', '--psf')]
     infile = args[0]
     refname = args[1]
     subclass = zuds.SingleEpochSubtraction
@@ -238,7 +265,7 @@ def main(argv):
     for fn in imgs:
         try:
             do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
-                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask, maglim=maglim)
+                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask, maglim=maglim, psf=psf, psfref=psfref)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

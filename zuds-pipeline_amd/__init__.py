@@ -37,7 +37,8 @@ from .lightcurve import *
 from .alert import *
 from .scamp import *
 from .photcal import *
-from . import synth, fits, scamp, lightcurve, photcal
+from .psf import *
+from . import synth, fits, scamp, lightcurve, photcal, psf
 
 # same DB-free entry points as the reference
 def init_db(*args, **kwargs):

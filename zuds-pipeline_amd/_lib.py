@@ -183,6 +183,12 @@ class zm_lc_image(C.Structure):
                 ('nx', C.c_int32), ('ny', C.c_int32)]
 
 
+class zm_psf_image(C.Structure):
+    """One image of ``zm_psf_photometry_batch_dev`` (include/zudsmi.h): a ``zm_lc_image``, then its model."""
+    _fields_ = [('img', C.c_void_p), ('rms', C.c_void_p), ('mask', C.c_void_p), ('wcs', zm_wcs),
+                ('nx', C.c_int32), ('ny', C.c_int32), ('model', C.c_void_p), ('half', C.c_int32), ('pad_', C.c_int32)]
+
+
 ASTROM_STATUS = ('OK', 'TOO_FEW', 'AMBIGUOUS', 'SINGULAR', 'NOT_CONVERGED')      # ZM_ASTROM_*
 RB_CHUNK = 128                                         # ZM_RB_CHUNK
 RB_CONV2D, RB_MAXPOOL, RB_FLATTEN, RB_DENSE = 1, 2, 3, 4
@@ -198,6 +204,9 @@ AUTO_CROWDED = 8                                       # flags_auto bit of the m
 GROWTH_NAPER_MAX, GROWTH_ROUT_MAX, CLIPMED_NMAX = 8, 20.0, 16384      # ZM_GROWTH_NAPER_MAX, ZM_GROWTH_ROUT_MAX, ZM_CLIPMED_NMAX
 GROWTH_BAD, GROWTH_SATURATED, GROWTH_NONFINITE, GROWTH_BOXCLIP, GROWTH_ANNCLIP, GROWTH_FEWSKY, GROWTH_BADPOS = \
     1, 2, 4, 8, 16, 32, 64                             # flags of zm_growth (ZM_GROWTH_*)
+PSF_HALF_MAX = 15                                      # ZM_PSF_HALF_MAX
+PSF_BAD, PSF_NONFINITE, PSF_BADRMS, PSF_CLIPPED, PSF_LOWCOVER, PSF_SINGULAR, PSF_BADPOS = \
+    1, 2, 4, 8, 16, 32, 64                             # flags of zm_psf_photometry (ZM_PSF_*)
 HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4         # zm_hp_info.status bits (include/zudsmi.h)
 
 
@@ -306,6 +315,16 @@ _SIGS = {
     'zm_clipped_median': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, _P]),
     'zm_clipped_median_dev': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_int, _P]),
     'zm_maglim_dev': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_double, C.c_int, _P]),
+    'zm_psf_build': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double,
+                               C.c_double, C.c_int, C.c_int, _P, _P, _P, C.c_int64]),
+    'zm_psf_build_dev': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double,
+                                   C.c_double, C.c_int, C.c_int, _P, _P, _P, C.c_int64]),
+    'zm_psf_photometry': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int,
+                                    C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'zm_psf_photometry_dev': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int,
+                                        C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'zm_psf_photometry_batch_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_psf_image), _P, _P, C.c_int64, C.c_int, _P, _P,
+                                              C.c_int32, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'zm_extract_params_default': (None, [C.POINTER(zm_extract_params)]),
     'zm_extract_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
                                  C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -105,7 +105,7 @@ struct zm_ctx {
     hipEvent_t bk_stats_event = nullptr;
     bool bk_stats_event_valid = false;
     int cl_npre = 0;                           // objects before CLEAN of the last zm_extract_clean call (slot "cl_stats")
-    hipEvent_t lc_tab_event = nullptr;         // behind the last copy out of the pinned image table of lightcurve.hip
+    hipEvent_t lc_tab_event = nullptr;         // behind the last copy out of a pinned image table: lightcurve.hip's ("lc_tab_h") or psf.hip's ("psf_tab_h"); each call waits for it before it rewrites its own table
     bool timing = false;
     std::string timing_only;                   // non-empty: only this scope is timed
     std::map<std::string, zm_timer_slot> timers;

@@ -175,15 +175,70 @@ class CalibratedImage(CalibratableImage):
         """The ``ForcedPhotometry`` points made on this image so far (the reference's relationship, a plain list)."""
         return self.__dict__.setdefault('_forced_photometry', [])
 
-    def force_photometry(self, sources, assume_background_subtracted=False, use_cutout=False, direct_load=None):
+    @property
+    def psf_model(self):
+        """The PSF model of this image (``psf.PSFModel``): the one ``build_psf`` made or that was assigned, else the sibling
+        ``*.psf.fits`` when there is one, else None."""
+        if '_psf_model' not in self.__dict__:
+            from .psf import PSFModel
+            path = getattr(self, 'local_path', None)
+            sibling = None if not path else str(path).replace('.fits', '.psf.fits')
+            self.__dict__['_psf_model'] = PSFModel.from_file(sibling) if sibling and os.path.exists(sibling) else None
+        return self.__dict__['_psf_model']
+
+    @psf_model.setter
+    def psf_model(self, model):
+        self.__dict__['_psf_model'] = model
+
+    def build_psf(self, stars=None, psf_kws=None, engine=None):
+        """Build the PSF model from the image's own stars, or a catalogue's (``psf.build_psf``; ``psf_kws``: ``-KEY value``
+        pairs as ``psf.psf_settings`` takes them; ``PSFREF_NAME`` names the catalogue when ``stars`` is None).  The model
+        becomes ``psf_model`` and its cards go into the header; nothing is saved.  Returns the dict of ``psf.build_psf``."""
+        from . import psf as _psf
+        st = _psf.psf_settings(psf_kws)
+        ref = st.pop('psfref')
+        res = _psf.build_psf(self, stars=stars if stars is not None else ref, engine=engine, **st)
+        self.psf_model = res['psf']
+        if self.header_comments is None:
+            self.header_comments = {}
+        for key, value, comment in res['cards']:
+            self.header[key] = value
+            self.header_comments[key] = comment
+        return res
+
+    def force_photometry(self, sources, assume_background_subtracted=False, use_cutout=False, direct_load=None,
+                         method='aperture', fit_sky=None):
         """Force aperture photometry at the locations of ``sources`` (``zuds/image.py:344-377``): one
         ``ForcedPhotometry`` per source, in order.  Assumes that calibration has already been done.  The points are
         returned, not recorded: the caller adds them to ``forced_photometry`` as the reference adds them to its
-        session."""
+        session.
+
+        ``method='psf'``: a fit of ``psf_model`` in place of the aperture sum (``psf.psf_photometry``), with ``zp = MAGZP +
+        PSFCOR``; ``fit_sky`` defaults to fitting a constant unless ``assume_background_subtracted``.  ``flags`` are then
+        those of the fit (``psf.PSF_FLAGS``)."""
         from .photometry import ForcedPhotometry, aperture_photometry
+        if method not in ('aperture', 'psf'):
+            raise ValueError(f'force_photometry: method {method!r} is neither \'aperture\' nor \'psf\'')
         sources = np.atleast_1d(sources)
         ra = [source.ra for source in sources]
         dec = [source.dec for source in sources]
+        if method == 'psf':
+            from .psf import psf_photometry
+            model = self.psf_model
+            if model is None:
+                raise RuntimeError(f'"{self.basename}" has no PSF model: build_psf() it, or put its *.psf.fits beside it')
+            cor = model.cards.get('PSFCOR', self.header.get('PSFCOR'))
+            if cor is None or 'MAGZP' not in self.header:
+                raise RuntimeError(f'"{self.basename}" has no MAGZP / PSFCOR: the PSF fluxes would have no zero point')
+            x, y = self.wcs.all_world2pix(ra, dec, 0)
+            sky = (not assume_background_subtracted) if fit_sky is None else fit_sky
+            res = psf_photometry(self, x, y, model, fit_sky=int(bool(sky)))
+            jd = self.header.get('OBSJD')
+            fc = 'z' + str(self.header['FILTER'])[-1] if 'FILTER' in self.header else None
+            return [ForcedPhotometry(flux=float(res['flux'][k]), fluxerr=float(res['fluxerr'][k]), flags=int(res['flags'][k]),
+                                     image=self, ra=r, dec=d, source=source, zp=float(self.header['MAGZP']) + float(cor),
+                                     obsjd=None if jd is None else float(jd), filtercode=fc)
+                    for k, (source, r, d) in enumerate(zip(sources, ra, dec))]
         result = aperture_photometry(self, ra, dec, apply_calibration=True,
                                      assume_background_subtracted=assume_background_subtracted,
                                      use_cutout=use_cutout, direct_load=direct_load)

@@ -103,7 +103,20 @@ def _resident(im, torch, device):
     return img, rms, mask, w, ny, nx
 
 
-def forced_photometry_batch(images, ra, dec, done=None, engine=None, radius=APERTURE_RADIUS):
+def _psf_of(im):
+    """The ``PSFModel`` of one image of a PSF batch: a dict's ``psf``, an image object's ``psf_model``."""
+    from .psf import PSFModel
+    psf = im.get('psf') if isinstance(im, dict) else getattr(im, 'psf_model', None)
+    if psf is None:
+        raise ValueError('forced_photometry_batch: method=\'psf\' needs a model for every image (the dict\'s `psf`, '
+                         'the image\'s `psf_model`)')
+    if not isinstance(psf, PSFModel):
+        psf = PSFModel(psf)
+    return psf
+
+
+def forced_photometry_batch(images, ra, dec, done=None, engine=None, radius=APERTURE_RADIUS, method='aperture',
+                            fit_radius=None, fit_sky=0, bad_bits=None):
     """Forced photometry of every (image, source) pair whose source lies inside the image's footprint: one join and one
     launch for the whole batch (``zm_footprint_join_dev``, ``zm_forced_photometry_batch_dev``).
 
@@ -112,8 +125,19 @@ def forced_photometry_batch(images, ra, dec, done=None, engine=None, radius=APER
     footprint is that of the plane: NAXIS of the WCS is taken from it.  ``done``: pairs ``(image index, source index)`` to
     leave out (see ``drop_done``).  Returns a dict of arrays with one row per pair, images in order and sources ascending
     within an image: ``image``, ``source``, ``x``, ``y`` (0-based pixels), ``flux``, ``fluxerr``, ``flags``; and
-    ``offsets`` (int64 [nimg + 1])."""
+    ``offsets`` (int64 [nimg + 1]).
+
+    ``method='psf'``: a linear fit of each image's PSF model in place of the aperture sum (``zm_psf_photometry_batch_dev``;
+    DESIGN.md, "PSF photometry"); any other value than 'aperture' or 'psf' raises ``ValueError``.  An image dict carries
+    its model under ``psf`` (a ``PSFModel`` or its array), an image object as ``psf_model``.  ``fit_radius``: pixels;
+    None takes the ``PSFFITR`` card the models carry (6 without one), and models that disagree on it are an error: say
+    which radius is meant.  ``fit_sky``: fit a constant beside the flux.  ``bad_bits``: the mask bits that take a pixel out
+    of a fit (default ``BAD_SUM``).  ``flags`` are then those of the fit (``psf.PSF_FLAGS``) and the table gains ``chi2``,
+    ``npix``, ``cover`` and ``sky``.  ``radius`` belongs to the aperture, ``fit_radius`` / ``fit_sky`` / ``bad_bits`` to
+    the fit."""
     import torch
+    if method not in ('aperture', 'psf'):
+        raise ValueError(f'forced_photometry_batch: method {method!r} is neither \'aperture\' nor \'psf\'')
     eng = engine or get_engine()
     device = torch.device('cuda', eng.device)
     ra = _f64(ra, 'ra')
@@ -150,6 +174,9 @@ def forced_photometry_batch(images, ra, dec, done=None, engine=None, radius=APER
         d_off = torch.from_numpy(offsets).to(device)
         d_idx = torch.from_numpy(src_idx).to(device) if npairs else d_idx
         torch.cuda.synchronize(device)
+    if method == 'psf':
+        return _psf_batch(eng, torch, device, images, planes, wcs, d_off, d_idx, offsets, src_idx, npairs, nsrc, d_ra, d_dec,
+                          fit_radius, fit_sky, bad_bits)
     res = torch.empty((4, max(npairs, 1)), dtype=torch.float64, device=device)
     flg = torch.empty(max(npairs, 1), dtype=torch.int32, device=device)
     check(eng.L.zm_forced_photometry_batch_dev(eng.ctx, nimg, recs, d_off.data_ptr(), d_idx.data_ptr(), npairs, nsrc,
@@ -163,12 +190,47 @@ def forced_photometry_batch(images, ra, dec, done=None, engine=None, radius=APER
                 flags=flg[:npairs].cpu().numpy().copy(), offsets=offsets)
 
 
-def photometry_rows(table, headers, ra, dec, source_ids=None, image_ids=None):
+def _psf_batch(eng, torch, device, images, planes, wcs, d_off, d_idx, offsets, src_idx, npairs, nsrc, d_ra, d_dec, fit_radius,
+               fit_sky, bad_bits):
+    """The launch of ``forced_photometry_batch(method='psf')`` behind the join."""
+    from .constants import BAD_SUM
+    nimg = len(planes)
+    psfs = [_psf_of(im) for im in images]
+    if fit_radius is None:
+        radii = sorted({p.fit_radius for p in psfs})
+        if len(radii) > 1:
+            raise ValueError(f'forced_photometry_batch: the models of this batch carry different PSFFITR ({radii}): pass fit_radius')
+        fit_radius = radii[0] if radii else 6.0
+    models = [torch.from_numpy(p.data).to(device) for p in psfs]
+    recs = (_lib.zm_psf_image * max(nimg, 1))()
+    for k, (img, rms, mask, w, ny, nx) in enumerate(planes):
+        recs[k].img, recs[k].rms, recs[k].mask = img.data_ptr(), rms.data_ptr() if rms is not None else None, \
+            mask.data_ptr() if mask is not None else None
+        recs[k].wcs, recs[k].nx, recs[k].ny = wcs[k], nx, ny
+        recs[k].model, recs[k].half = models[k].data_ptr(), psfs[k].half
+    torch.cuda.synchronize(device)
+    res = torch.empty((7, max(npairs, 1)), dtype=torch.float64, device=device)
+    ints = torch.empty((2, max(npairs, 1)), dtype=torch.int32, device=device)
+    check(eng.L.zm_psf_photometry_batch_dev(eng.ctx, nimg, recs, d_off.data_ptr(), d_idx.data_ptr(), npairs, nsrc,
+                                            d_ra.data_ptr(), d_dec.data_ptr(), int(BAD_SUM if bad_bits is None else bad_bits),
+                                            float(fit_radius), int(bool(fit_sky)), *(res[k].data_ptr() for k in range(7)),
+                                            ints[0].data_ptr(), ints[1].data_ptr()), 'zm_psf_photometry_batch_dev')
+    eng.synchronize()
+    r = res[:, :npairs].cpu().numpy()
+    i = ints[:, :npairs].cpu().numpy()
+    return dict(image=np.repeat(np.arange(nimg, dtype=np.int32), np.diff(offsets)), source=src_idx.astype(np.int32),
+                x=r[0].copy(), y=r[1].copy(), flux=r[2].copy(), fluxerr=r[3].copy(), flags=i[1].copy(), offsets=offsets,
+                chi2=r[4].copy(), npix=i[0].copy(), cover=r[6].copy(), sky=r[5].copy())
+
+
+def photometry_rows(table, headers, ra, dec, source_ids=None, image_ids=None, method='aperture'):
     """The rows ``scripts/dophot.py`` writes (``scripts/dophot.py:144-156``) from the table of
     ``forced_photometry_batch``: one dict per pair with the keys of ``PHOT_CSV_COLUMNS``.  ``headers``: the header of
     each image: ``zp = MAGZP + APCOR4``, ``obsjd`` and ``filtercode`` ('z' + the last letter of FILTER) as
-    ``raw_aperture_photometry`` takes them."""
-    zp = [h['MAGZP'] + h[APER_KEY] for h in headers]
+    ``raw_aperture_photometry`` takes them.  ``method='psf'`` (a table of PSF fits): ``zp = MAGZP + PSFCOR``."""
+    if method not in ('aperture', 'psf'):
+        raise ValueError(f'photometry_rows: method {method!r} is neither \'aperture\' nor \'psf\'')
+    zp = [h['MAGZP'] + h[APER_KEY if method == 'aperture' else 'PSFCOR'] for h in headers]
     jd = [h.get('OBSJD') for h in headers]
     fc = ['z' + str(h['FILTER'])[-1] if 'FILTER' in h else None for h in headers]
     rows = []

@@ -176,12 +176,14 @@ class Source(object):
         have = {id(p.image) for p in self.forced_photometry}
         return [im for im in self.images(images, engine=engine) if id(im) not in have]
 
-    def force_photometry(self, images=(), assume_background_subtracted=True):
+    def force_photometry(self, images=(), assume_background_subtracted=True, method='aperture'):
         """Photometry of this source on every image of ``images`` that holds it and has none yet
-        (``zuds/source.py:136-153``); the points are returned, not recorded."""
+        (``zuds/source.py:136-153``); the points are returned, not recorded.  ``method='psf'``: fits of each image's
+        ``psf_model`` (``CalibratedImage.force_photometry``)."""
         out = []
         for im in self.unphotometered_images(images):
-            out.extend(im.force_photometry(self, assume_background_subtracted=assume_background_subtracted, use_cutout=True))
+            kw = {} if method == 'aperture' else {'method': method}
+            out.extend(im.force_photometry(self, assume_background_subtracted=assume_background_subtracted, use_cutout=True, **kw))
         return out
 
     def __repr__(self):

@@ -1,8 +1,9 @@
 """Scenes for the CLEAN tests: the smallest inputs at which each part of the operator can go wrong.
 
-Test infrastructure.  Every scene is (img, sigma, keyword arguments of the extraction); no scene carries a non-finite
-pixel.  Moffat sources are ``amp (1 + r^2 / w^2)^-b`` with ``w = fwhm / (2 sqrt(2^(1/b) - 1))``, centres 0-based, noise
-``default_rng(seed).normal``.  ``reference(name, ...)`` computes the numpy restatement once per process.
+Test infrastructure.  Every scene is (img, sigma, keyword arguments of the extraction, which may carry a ``bad`` and a
+``flag`` plane).  The scenes of ``PLANES`` are those of tests/deblend_scenes.py at the frame's edges and with bad, flagged
+and non-finite pixels, and two of their own (``shred``, ``shred_corner``).  Moffat sources are ``amp (1 + r^2 / w^2)^-b``
+with ``w = fwhm / (2 sqrt(2^(1/b) - 1))``, centres 0-based, noise ``default_rng(seed).normal``.  ``reference(name, ...)`` computes the numpy restatement once per process.
 """
 import functools
 
@@ -75,7 +76,25 @@ def shapes(k):
     return img, sigma, dict(filter=False, detect_minarea=k)
 
 
-SCENES = {'halo1': lambda: halo(1), 'halo2': lambda: halo(2), 'halo3': lambda: halo(3), 'halo_pair': halo_pair, 'stars40': stars40,
+def shred(cx, cy):
+    """48 x 48, no filter: a blend of two stars (2000 at (cx, cy), 1500 6 px below it), a 3 x 3 hole of bad pixels in the
+    first one's wing 7 .. 9 px to its right, and beside the hole, cut off from the star by it, a shred of 3 x 2 pixels at
+    1.75 (0.25 above the threshold).  Deblending at nthresh 32 splits the blend; CLEAN folds the shred into the first
+    star, which then borders the hole on both sides.  ``shred(4, 4)`` sits in the frame's corner."""
+    img = ds.gaussians(48, 48, [(cx, cy, 2000.0, 2.0), (cx, cy + 6, 1500.0, 2.0)]).astype(np.float32)
+    bad = np.zeros((48, 48), np.uint8)
+    bad[cy - 1:cy + 2, cx + 7:cx + 10] = 1
+    img[cy - 1:cy + 2, cx + 10:cx + 12] = 1.75
+    return img, np.ones((48, 48), np.float32), dict(filter=False, bad=bad)
+
+
+SHREDS = {'shred': lambda: shred(20, 20), 'shred_corner': lambda: shred(4, 4)}
+# the scenes with edges, bad pixels, flags and poison: each runs deblended at nthresh 32 and at nthresh 8
+PLANES = list(ds.EDGE_SCENES) + list(ds.BAD_SCENES) + list(ds.POISON_SCENES) + list(SHREDS)
+PLANES_NTHRESH = (32, 8)
+
+SCENES = {**{name: (lambda name=name: ds.scene(name)) for name in PLANES if name not in SHREDS}, **SHREDS,
+          'halo1': lambda: halo(1), 'halo2': lambda: halo(2), 'halo3': lambda: halo(3), 'halo_pair': halo_pair, 'stars40': stars40,
           'two_equal': two_equal, 'shapes1': lambda: shapes(1), 'shapes5': lambda: shapes(5), 'shapes9': lambda: shapes(9),
           'noisy_field': ds.noisy_field}
 # the scenes whose full call is compared with the restatement bit for bit: test_clean_ref.py checks their gap
@@ -86,8 +105,9 @@ BITWISE = [(name, db) for name in ('halo1', 'halo2', 'halo3') for db in (False, 
 @functools.lru_cache(maxsize=None)
 def scene(name):
     img, sigma, kw = SCENES[name]()
-    img.setflags(write=False)
-    sigma.setflags(write=False)
+    for a in (img, sigma, kw.get('bad'), kw.get('flag')):
+        if a is not None:
+            a.setflags(write=False)
     return img, sigma, kw
 
 
@@ -99,9 +119,10 @@ def ref_kw(kw):
 
 @functools.lru_cache(maxsize=None)
 def reference(name, deblend=False, param=1.0, reverse=False):
+    """``deblend``: False, True (nthresh 32) or another nthresh."""
     img, sigma, kw = scene(name)
-    return cr.clean(img, sigma, param=param, deblend=dict(nthresh=32, mincont=0.005) if deblend else None, reverse=reverse,
-                    **ref_kw(kw))
+    db = dict(nthresh=32 if deblend is True else int(deblend), mincont=0.005) if deblend else None
+    return cr.clean(img, sigma, kw.get('bad'), kw.get('flag'), param=param, deblend=db, reverse=reverse, **ref_kw(kw))
 
 
 TABLE_SIZES = (1, 2, 255, 256, 257, 1000)               # either side of one tile of absorbers, and several tiles

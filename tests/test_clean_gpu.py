@@ -4,8 +4,11 @@ The per-object sums F, T and m, the decisions (``into``, ``root``), the segmenta
 PARENT_NUMBER and NMERGED are compared bit for bit.  The float columns are held to the bounds of
 tests/test_extract_gpu.py, figures printed before anything is asserted: 10 x the difference between the restatement's
 forward and reversed summation order, plus ``extract_ref.LIBM_ULPS`` spacings for THETA_IMAGE and FWHM_IMAGE; FLUX_APER and
-FLUXERR_APER to the aperture kernel's existing pin (rtol 1e-10, atol 1e-9).  No scene carries a non-finite pixel, so
-every row is compared in every column.
+FLUXERR_APER to the aperture kernel's existing pin (rtol 1e-10, atol 1e-9).  Every row is compared in every column: the
+NaN / +inf / -inf pattern of a float column must equal the restatement's, and outside the poisoned scenes every float must
+be finite.  The scenes of ``clean_scenes.PLANES`` - the frame's edges, bad pixels, a flag plane, non-finite pixels, and a
+shred beside a 3 x 3 hole that CLEAN folds into the star whose wing the hole lies in, once in the frame's corner - run
+deblended at nthresh 32 and at nthresh 8 (tests/test_clean_ref.py: their gaps, and that the planes change the map).
 
 Outcomes of the scenes (restatement and GPU alike): ``halo`` with seeds 1, 2, 3 goes from 6 / 16 / 15 objects to 3, the
 galaxy and the two stars, with smallest relative gaps 0.51 / 0.18 / 0.24; ``stars40`` keeps its 23 objects, ``two_equal``
@@ -22,6 +25,7 @@ import pytest
 
 import clean_ref as cr
 import clean_scenes as cs
+import deblend_scenes as ds
 import extract_ref as xr
 from test_clean_ref import chain_table
 from test_extract_gpu import APER_COLUMNS
@@ -32,35 +36,30 @@ DEBLEND = dict(nthresh=32, mincont=0.005)
 
 
 def run(engine, name, deblend=False, **more):
+    """``deblend``: False, True (nthresh 32) or another nthresh."""
     img, sigma, kw = cs.scene(name)
-    return engine.extract(img, sigma, full=True, deblend=DEBLEND if deblend else False, clean=more.pop('clean', True),
-                          **kw, **more)
+    db = dict(DEBLEND, nthresh=32 if deblend is True else int(deblend)) if deblend else False
+    return engine.extract(img, sigma, full=True, deblend=db, clean=more.pop('clean', True), **kw, **more)
 
 
 def int_columns(deblend):
     return xr.INT_COLUMNS + (['PARENT_NUMBER'] if deblend else []) + ['NMERGED']
 
 
-def compare(engine, name, deblend=False, **more):
+def compare(engine, name, deblend=False, finite=True, **more):
+    """``finite``: every float of both tables must be finite (every scene but the poisoned ones).  Otherwise the NaN / inf
+    pattern of every float column must equal the restatement's; no row and no column is left out either way."""
     got = run(engine, name, deblend, **more)
     ref, rev = cs.reference(name, deblend), cs.reference(name, deblend, reverse=True)
     assert got['status'] == 0
-    assert got['filtered'].tobytes() == np.ascontiguousarray(ref['filtered']).tobytes(), 'filtered plane'
+    ds.assert_same_plane(got['filtered'], ref['filtered'])
     assert np.array_equal(got['segm'], ref['segm']), 'segmentation map'
     t, r = got['table'], ref['table']
     assert got['nfound'] == len(r) == len(t)
     assert ('PARENT_NUMBER' in t.dtype.names) == bool(deblend)
     for c in int_columns(deblend):
         assert np.array_equal(t[c], r[c]), c
-    bounds = xr.order_bounds(r, rev['table'])
-    worst, fails = {}, []
-    for c in xr.FLOAT_COLUMNS:
-        assert np.isfinite(r[c]).all() and np.isfinite(t[c]).all(), c          # no row is left out
-        diff = np.abs(t[c] - r[c])
-        allow = 1e-10 * np.abs(r[c]) + 1e-9 if c in APER_COLUMNS else bounds[c] + xr.libm_allowance(c, r[c])
-        worst[c] = float(diff.max()) if len(diff) else 0.0
-        if (diff > allow).any():
-            fails.append((c, worst[c], bounds[c]))
+    worst, bounds, fails = ds.float_columns(t, r, rev['table'], APER_COLUMNS, finite)
     print(f'clean {name} deblend={deblend}: {len(ref["pre"]["table"])} -> {len(r)} objects, gap {ref["gap"]:.3g}; column '
           f'measured (order bound; libm allowance in spacings): '
           + ', '.join(f'{c} {worst[c]:.3g} ({bounds[c]:.3g}; {xr.LIBM_ULPS.get(c, 0)})' for c in xr.FLOAT_COLUMNS))
@@ -304,6 +303,40 @@ def test_limits_runs_and_entry_points(engine):
     for bad in (dict(param=0.01), dict(param=float('inf')), dict(beta=1.0)):
         with pytest.raises(ValueError):
             engine.extract(img, sigma, clean=bad)
+
+
+@pytest.mark.parametrize('nthresh', cs.PLANES_NTHRESH)
+@pytest.mark.parametrize('name', cs.PLANES)
+def test_edges_bad_pixels_flags_and_poison(engine, name, nthresh):
+    """CLEAN over the scenes with edges, bad pixels, flags and poison (clean_ref.clean(..., bad=, flag=)), deblended at
+    nthresh 32 and 8.  Stars are not each other's shreds: only the shred beside the hole is absorbed."""
+    got, ref = compare(engine, name, nthresh, finite=name not in ds.POISON_SCENES, clean=dict(param=1.0))
+    t = got['table']
+    if name in cs.SHREDS:
+        assert t['NMERGED'].tolist() == ([2, 1] if nthresh == 32 else [2]) and t['FLAGS_WEIGHT'][0] == 1
+        assert ((t['XMIN_IMAGE'][0], t['YMIN_IMAGE'][0]) == (1, 1)) == (name == 'shred_corner')
+    else:
+        assert len(t) == ds.EXPECT[name][4] and (t['NMERGED'] == 1).all()
+
+
+def test_planes_on_the_device_and_two_runs(engine):
+    hipmem = importlib.import_module('zuds-pipeline_amd.hipmem')
+    img, sigma, kw = cs.scene('shred_corner')
+    flag = (np.arange(48 * 48, dtype=np.int32).reshape(48, 48) % 5 == 0) * 8
+    a, b = (run(engine, 'shred_corner', True, flag=flag) for _ in range(2))
+    assert a['table'].tobytes() == b['table'].tobytes() and a['segm'].tobytes() == b['segm'].tobytes()
+    assert a['table']['NMERGED'].tolist() == [2, 1] and a['table']['IMAFLAGS_ISO'].tolist() == [8, 8]
+    bufs = []
+    for arr, dt in ((img, np.float32), (sigma, np.float32), (kw['bad'], np.uint8), (flag, np.int32)):
+        arr = np.ascontiguousarray(arr, dt)
+        d = hipmem.DeviceBuffer(arr.nbytes)
+        d.upload(arr)
+        bufs.append(d)
+    dseg = hipmem.DeviceBuffer(a['segm'].nbytes)
+    dtab, nfound = engine.extract_dev(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, 48, 48, segm=dseg.ptr, deblend=DEBLEND,
+                                      clean=True, filter=False)
+    assert nfound == 2 and dtab.dtype == a['table'].dtype and dtab.tobytes() == a['table'].tobytes()
+    assert np.array_equal(dseg.download(np.int32, a['segm'].shape), a['segm'])
 
 
 # ---- through the layers ---------------------------------------------------------------------------------------------

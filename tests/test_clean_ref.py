@@ -129,3 +129,51 @@ def test_tables_compared_at_other_exponents_have_a_gap(n, param):
     into, _, gap = cr.decide(rows, F, T, m, param)
     print(f'n {n} param {param}: {int((into > 0).sum())} absorbed, gap {gap:.3g}')
     assert gap > cr.GAP_MIN
+
+
+# ---- the scenes at the frame's edges and with bad, flagged and poisoned pixels (clean_scenes.PLANES) --------------------
+@pytest.mark.parametrize('nthresh', cs.PLANES_NTHRESH)
+@pytest.mark.parametrize('name', cs.PLANES)
+def test_scenes_with_planes_are_what_they_claim(name, nthresh):
+    """Objects before and after, a gap wherever the GPU test compares bit for bit, and the same map in either order."""
+    import deblend_scenes as ds
+    import extract_ref as xr
+    r, rev = cs.reference(name, nthresh), cs.reference(name, nthresh, reverse=True)
+    t = r['table']
+    counts = (len(r['pre']['first']['table']), len(r['pre']['table']), len(t))
+    print(f'{name} nthresh {nthresh}: {counts[0]} first-pass -> {counts[1]} deblended -> {counts[2]} objects, gap {r["gap"]:.3g}, '
+          f'NMERGED {t["NMERGED"].tolist()}')
+    assert r['gap'] > cr.GAP_MIN
+    assert np.array_equal(r['segm'], rev['segm']) and np.array_equal(r['into'], rev['into'])
+    for c in xr.INT_COLUMNS + ['PARENT_NUMBER', 'NMERGED']:
+        assert np.array_equal(t[c], rev['table'][c]), c
+    if name in cs.SHREDS:
+        assert counts == ((2, 3, 2) if nthresh == 32 else (2, 2, 1))
+    else:                                                 # stars are not each other's shreds: the deblended objects stay
+        assert counts[1:] == (ds.EXPECT[name][4], ds.EXPECT[name][4]) and counts[0] == ds.EXPECT[name][3]
+        assert (t['NMERGED'] == 1).all() and np.array_equal(r['segm'], r['pre']['segm'])
+    if name in ds.BAD_SCENES or name in ds.POISON_SCENES or name in cs.SHREDS:
+        # sensitivity: without the planes (and the poison) the map is another one
+        img, sigma, kw = ds.unmasked(name) if name not in cs.SHREDS else cs.scene(name)
+        plain = cr.clean(img, sigma, deblend=dict(nthresh=nthresh, mincont=0.005), **cs.ref_kw(kw))
+        assert not np.array_equal(plain['segm'], r['segm'])
+
+
+@pytest.mark.parametrize('name', list(cs.SHREDS))
+def test_a_shred_beside_a_hole_is_absorbed(name):
+    import scipy.ndimage as ndi
+    r = cs.reference(name, 32)
+    t, hole = r['table'], r['pre']['first']['bad']
+    assert hole.sum() == 9
+    ring = ndi.binary_dilation(hole, structure=np.ones((3, 3))) & ~hole
+    before, after = set(r['pre']['segm'][ring].tolist()) - {0}, set(r['segm'][ring].tolist()) - {0}
+    assert len(before) == 2 and len(after) == 1                               # the star and the shred; then one object
+    row = t[after.pop() - 1]
+    assert row['NMERGED'] == 2 and row['FLAGS_WEIGHT'] == 1 and (row['FLAGS'] & 2) and t['NMERGED'].tolist() == [2, 1]
+    assert t['FLAGS_WEIGHT'].tolist() == [1, 0]
+    shred = r['pre']['table'][int(np.flatnonzero(r['into'])[0])]
+    assert shred['ISOAREA_IMAGE'] == 6 and r['into'].tolist().count(0) == 2
+    if name == 'shred_corner':
+        assert (row['XMIN_IMAGE'], row['YMIN_IMAGE']) == (1, 1) and (row['FLAGS'] & 8)
+    else:
+        assert not (row['FLAGS'] & 8)

@@ -3,8 +3,18 @@
 The filtered plane, the segmentation map, every integer column and PARENT_NUMBER are compared bit for bit.  The float
 columns are held to the bounds of tests/test_extract_gpu.py, figures printed before anything is asserted: 10 x the
 difference between the restatement's forward and reversed summation order, plus ``extract_ref.LIBM_ULPS`` spacings for
-THETA_IMAGE and FWHM_IMAGE; FLUX_APER and FLUXERR_APER to the aperture kernel's existing pin (rtol 1e-10, atol 1e-9).  No
-scene carries a non-finite pixel, so every row is compared in every column.  Every test calls ``deblend=``.
+THETA_IMAGE and FWHM_IMAGE; FLUX_APER and FLUXERR_APER to the aperture kernel's existing pin (rtol 1e-10, atol 1e-9).
+Every row is compared in every column: the NaN / +inf / -inf pattern of a float column must equal the restatement's, and
+outside the poisoned scenes every float must be finite.  Where the restatement's filtered plane holds a NaN (``filter=False``
+over a NaN pixel) NaN-ness is compared instead of the bytes.  Every test calls ``deblend=``.
+
+The scenes added for the tree kernel's indexing (tests/deblend_scenes.py; tests/test_deblend_ref.py proves on the
+restatement that each reaches what it names): every accepted ``nthresh`` (2 .. 64; one scene changes its outcome between 2
+and 32, one between 32 and 64, one object occupies 51 of the 64 levels); bounding boxes of 1, 2 and 3 pixels' width and
+blocks on either side of the LDS limit, the thin ones hanging together through one diagonal step; blends on the right
+and bottom edge, in the four corners, frames that are one object (37 x 29, 31 x 29, 1 x 40, 40 x 1); bad pixels on a
+saddle, on the peak, along a diagonal line, as holes in a wing, along the frame's edge; a flag plane; and NaN, +inf, -inf
+in ``img`` and NaN, 0, -1 in ``sigma`` at the saddle and in the hole, measured with an aperture that reaches them.
 
 Outcomes of the scenes (restatement and GPU alike): pairs 3 and 4 px apart stay one object, 5, 6 and 8 px apart give
 two; the companion of 0.4 % of the flux stays merged, the one of 1.2 % splits; three nested peaks give three objects; the
@@ -33,24 +43,18 @@ def run(engine, name, **more):
     return engine.extract(img, sigma, full=True, deblend=db or True, **ex, **more)
 
 
-def compare(engine, name):
+def compare(engine, name, finite=True):
+    """``finite``: every float of both tables must be finite (every scene but the poisoned ones).  Otherwise the NaN / inf
+    pattern of every float column must equal the restatement's; no row and no column is left out either way."""
     got, ref, rev = run(engine, name), ds.reference(name), ds.reference(name, reverse=True)
     assert got['status'] == 0
-    assert got['filtered'].tobytes() == np.ascontiguousarray(ref['filtered']).tobytes(), 'filtered plane'
+    ds.assert_same_plane(got['filtered'], ref['filtered'])
     assert np.array_equal(got['segm'], ref['segm']), 'segmentation map'
     t, r = got['table'], ref['table']
     assert got['nfound'] == len(r) == len(t)
     for c in INT_COLUMNS:
         assert np.array_equal(t[c], r[c]), c
-    bounds = xr.order_bounds(r, rev['table'])
-    worst, fails = {}, []
-    for c in xr.FLOAT_COLUMNS:
-        assert np.isfinite(r[c]).all() and np.isfinite(t[c]).all(), c          # no row is left out
-        diff = np.abs(t[c] - r[c])
-        allow = 1e-10 * np.abs(r[c]) + 1e-9 if c in APER_COLUMNS else bounds[c] + xr.libm_allowance(c, r[c])
-        worst[c] = float(diff.max()) if len(diff) else 0.0
-        if (diff > allow).any():
-            fails.append((c, worst[c], bounds[c]))
+    worst, bounds, fails = ds.float_columns(t, r, rev['table'], APER_COLUMNS, finite)
     print(f'deblend {name}: {len(ref["first"]["table"])} -> {len(r)} objects; column measured (order bound; libm allowance '
           f'in spacings): ' + ', '.join(f'{c} {worst[c]:.3g} ({bounds[c]:.3g}; {xr.LIBM_ULPS.get(c, 0)})'
                                         for c in xr.FLOAT_COLUMNS))
@@ -137,6 +141,68 @@ def test_boxes_on_either_side_of_the_lds_limit(engine, width):
         == (width, 32) and t['ISOAREA_IMAGE'].sum() == 32 * width
 
 
+@pytest.mark.parametrize('nthresh', ds.NTHRESH)
+@pytest.mark.parametrize('base', list(ds.NTHRESH_OBJECTS))
+def test_every_nthresh(engine, base, nthresh):
+    """nlev = nthresh sets the length of u[] / hist[] (full at 64), the number of square roots and every per-level loop."""
+    got, ref = compare(engine, f'{base}@{nthresh}')
+    assert len(got['table']) == ds.NTHRESH_OBJECTS[base][nthresh]
+    assert len(run(engine, base)['table']) == ds.NTHRESH_OBJECTS[base][32]     # the engine is not left at another nthresh
+
+
+@pytest.mark.parametrize('name', list(ds.BOX_SCENES))
+def test_box_shapes_around_the_lds_limit(engine, name):
+    """1, 2 and 3 pixels wide and blocks, in both forms of the tree kernel; the thin ones hold a diagonal-only connection."""
+    got, ref = compare(engine, name)
+    t = got['table']
+    bw, bh, npix, _, n = ds.EXPECT[name]
+    assert len(t) == n == 2 and t['ISOAREA_IMAGE'].sum() == npix and ((t['FLAGS'] & 2) != 0).all()
+    assert (t['XMAX_IMAGE'].max() - t['XMIN_IMAGE'].min() + 1, t['YMAX_IMAGE'].max() - t['YMIN_IMAGE'].min() + 1) == (bw, bh)
+
+
+@pytest.mark.parametrize('name', list(ds.SINGLE_LINES))
+def test_single_peak_lines_equal_the_default_call(engine, name):
+    """One thin line on either side of DB_CELLS that does not split: table and map are the default call's bit for bit."""
+    got, ref = compare(engine, name)
+    assert len(got['table']) == 1 and ref['nsplit'] == 0 and got['table']['ISOAREA_IMAGE'][0] == ds.EXPECT[name][2]
+    assert_equals_default_call(engine, name, got)
+
+
+@pytest.mark.parametrize('name', list(ds.EDGE_SCENES))
+def test_frame_edges(engine, name):
+    """Right and bottom edge, the four corners, frames that are one object (global and LDS form), one column, one row."""
+    got, ref = compare(engine, name)
+    t = got['table']
+    assert len(t) == ds.EXPECT[name][4] and ((t['FLAGS'] & 2) != 0).all() and ((t['FLAGS'] & 8) != 0).any()
+    ny, nx = got['segm'].shape
+    if name.startswith('frame'):
+        assert (got['segm'] > 0).all() and t['ISOAREA_IMAGE'].sum() == nx * ny and ((t['FLAGS'] & 8) != 0).all()
+
+
+@pytest.mark.parametrize('name', list(ds.BAD_SCENES))
+def test_bad_pixels_and_flags(engine, name):
+    """``bad`` and ``flag`` planes as DeviceSubtraction.extract always passes them; the bad pixels hold finite values, so
+    every float of the table must be finite."""
+    got, ref = compare(engine, name, finite=True)
+    t, kw = got['table'], ds.scene(name)[2]
+    assert len(t) == ds.EXPECT[name][4] and not (got['segm'][kw['bad'] != 0] != 0).any()
+    plain = engine.extract(*ds.scene(name)[:2], full=True, deblend=True, filter=kw['filter'])      # the plane matters
+    assert not np.array_equal(plain['segm'], got['segm'])
+    if 'flags' in name:
+        assert t['IMAFLAGS_ISO'].tolist() == [0, 0x40000010] and t['FLAGS_WEIGHT'].tolist() == [1, 0]
+
+
+@pytest.mark.parametrize('name', list(ds.POISON_SCENES))
+def test_poisoned_pixels(engine, name):
+    """NaN, +inf, -inf in img; NaN, 0, -1 in sigma, at the saddle and as a 3 x 3 hole: they are bad pixels to the map, and
+    the aperture of radius 7 sums over whatever they hold - the NaN / inf pattern must be the restatement's."""
+    got, ref = compare(engine, name, finite=False)
+    t = got['table']
+    assert len(t) == ds.EXPECT[name][4] == 2 and (t['FLAGS'] & 16).any()
+    column = 'FLUX_APER' if name.startswith('img') else 'FLUXERR_APER'
+    assert name.startswith(('sig0', 'signeg')) or not np.isfinite(t[column]).all()
+
+
 def test_limits(engine):
     got, _ = compare(engine, 'edge')
     assert len(got['table']) == 2 and ((got['table']['FLAGS'] & 8) != 0).all()
@@ -176,6 +242,24 @@ def test_entry_points_and_runs_give_the_same_bytes(engine):
     dtab, nfound = engine.extract_dev(bufs[0].ptr, bufs[1].ptr, None, None, 128, 128, segm=dseg.ptr, deblend=True)
     assert nfound == 20 and dtab.dtype == a['table'].dtype and dtab.tobytes() == a['table'].tobytes()
     assert np.array_equal(dseg.download(np.int32, a['segm'].shape), a['segm'])
+    # ... and with a bad and a flag plane on the device, as DeviceSubtraction.extract calls it
+    for name in ('bad_flags.f1', 'bad_diag.f0'):
+        img, sigma, kw = ds.scene(name)
+        flag = kw.get('flag', np.arange(48 * 48, dtype=np.int32).reshape(48, 48) % 7)
+        a, b = (engine.extract(img, sigma, kw['bad'], flag, full=True, deblend=True, filter=kw['filter']) for _ in range(2))
+        assert a['table'].tobytes() == b['table'].tobytes() and a['segm'].tobytes() == b['segm'].tobytes()
+        assert a['table']['IMAFLAGS_ISO'].any() and a['table']['FLAGS_WEIGHT'].any()
+        bufs = []
+        for arr, dt in ((img, np.float32), (sigma, np.float32), (kw['bad'], np.uint8), (flag, np.int32)):
+            arr = np.ascontiguousarray(arr, dt)
+            d = hipmem.DeviceBuffer(arr.nbytes)
+            d.upload(arr)
+            bufs.append(d)
+        dseg = hipmem.DeviceBuffer(a['segm'].nbytes)
+        dtab, nfound = engine.extract_dev(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, 48, 48, segm=dseg.ptr, deblend=True,
+                                          filter=kw['filter'])
+        assert nfound == len(a['table']) and dtab.tobytes() == a['table'].tobytes()
+        assert np.array_equal(dseg.download(np.int32, a['segm'].shape), a['segm'])
 
 
 def test_wide_table_measures_the_sub_objects(engine):

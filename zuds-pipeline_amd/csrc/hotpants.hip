@@ -459,6 +459,39 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 // matrices go to Gp[cell][slice], k_hp_gram_sum adds them in slice order (deterministic).
 // As for the vectors: after the first round a cell's latency sets the kernel time.
 #define GR_SPLIT 8
+// G is symmetric, bit for bit: entry (i, j) and entry (j, i) are the same products a b = b a added in the same K
+// order (read back and compared for the 293 live cells of the benchmark's first round: 373 575 pairs, none
+// differs).  Of the 4 x 4 tiles of 16 x 16 only the ten of the lower triangle are computed, (NT <= 3) per wave; a tile
+// below the diagonal is also written transposed, so every reader of Gp / G finds the full matrix.
+// One K tile of the tiles (R0, C0) .. of a wave: the operand of a row block is read once (the reads of a block that
+// serves two tiles are the same expression and fold).
+template <int NT, int R0, int C0, int R1, int C1, int R2, int C2>
+static __device__ __forceinline__ void hp_gram_ktile(const double* L, int li, int lk, double4_t (&acc)[3]) {
+#pragma unroll
+    for (int kk = 0; kk < GR_KT / 4; ++kk) {
+        const double* Lk = L + li * GR_PITCH + 4 * kk + lk;
+        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(Lk[16 * R0 * GR_PITCH], Lk[16 * C0 * GR_PITCH], acc[0], 0, 0, 0);
+        if (NT > 1) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Lk[16 * R1 * GR_PITCH], Lk[16 * C1 * GR_PITCH], acc[1], 0, 0, 0);
+        if (NT > 2) acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(Lk[16 * R2 * GR_PITCH], Lk[16 * C2 * GR_PITCH], acc[2], 0, 0, 0);
+    }
+}
+// C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 reg
+template <int R, int C>
+static __device__ __forceinline__ void hp_gram_store(double* Gc, int li, int lk, const double4_t& a) {
+#pragma unroll
+    for (int rg = 0; rg < 4; ++rg) {
+        Gc[(size_t)(16 * R + lk + 4 * rg) * HP_MAXX + 16 * C + li] = a[rg];
+        if (R != C) Gc[(size_t)(16 * C + li) * HP_MAXX + 16 * R + lk + 4 * rg] = a[rg];
+    }
+}
+// the deal: 3 + 3 + 2 + 2 tiles; a row block's tiles stay together where they can (its operand is shared)
+#define GR_DEAL(sel, F) \
+    switch (sel) { \
+        case 0: F(3, 3, 0, 3, 1, 3, 2) break; \
+        case 1: F(3, 2, 0, 2, 1, 2, 2) break; \
+        case 2: F(2, 1, 0, 1, 1, 0, 0) break; \
+        default: F(2, 0, 0, 3, 3, 0, 0) break; \
+    }
 static __device__ __forceinline__ void hp_gram_body(const hp_plan& P, const double* __restrict__ X,
                                                  const int* __restrict__ need,
                                                  const int* __restrict__ active,
@@ -476,12 +509,15 @@ static __device__ __forceinline__ void hp_gram_body(const hp_plan& P, const doub
     const double* Xc = X + (size_t)cell * P.nX * P.npixp;
     const int wave = tid >> 6, lane = tid & 63;
     const int li = lane & 15, lk = lane >> 4;
+    // (a wave sits on the SIMD of its number: the workgroups that share a CU turn the deal, so that the SIMDs
+    // with three tiles are not the same ones for all of them)
+    const int sel = __builtin_amdgcn_readfirstlane((wave + blockIdx.x + blockIdx.y) & 3);
     const int ntile = P.npixp / GR_KT;                     // npixp is a multiple of GR_KT
     const int per = (ntile + GR_SPLIT - 1) / GR_SPLIT;
     const int kbeg = blockIdx.y * per * GR_KT, kend = min((int)(blockIdx.y + 1) * per, ntile) * GR_KT;
-    double4_t acc[4];
+    double4_t acc[3];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) acc[c] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < 3; ++c) acc[c] = (double4_t){0.0, 0.0, 0.0, 0.0};
     // a K tile = 64 rows x 32 columns = 8 doubles per thread: fetched into registers one tile
     // ahead (all eight loads in flight together, and under the matrix cores' work on the
     // current tile), stored to LDS after the barrier
@@ -504,25 +540,20 @@ static __device__ __forceinline__ void hp_gram_body(const hp_plan& P, const doub
         }
         __syncthreads();
         if (k0 + GR_KT < kend) fetch(k0 + GR_KT);
-#pragma unroll
-        for (int kk = 0; kk < GR_KT / 4; ++kk) {
-            double a = L[(16 * wave + li) * GR_PITCH + 4 * kk + lk];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                double b = L[(16 * c + li) * GR_PITCH + 4 * kk + lk];
-                acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[c], 0, 0, 0);
-            }
-        }
+#define GR_STEP(NT, R0, C0, R1, C1, R2, C2) hp_gram_ktile<NT, R0, C0, R1, C1, R2, C2>(L, li, lk, acc);
+        GR_DEAL(sel, GR_STEP)
+#undef GR_STEP
     }
-    // C/D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 reg
     double* Gc = Gp + ((size_t)cell * GR_SPLIT + blockIdx.y) * HP_MAXX * HP_MAXX;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg)
-            Gc[(size_t)(16 * wave + lk + 4 * rg) * HP_MAXX + 16 * c + li] = acc[c][rg];
+#define GR_OUT(NT, R0, C0, R1, C1, R2, C2) { \
+        hp_gram_store<R0, C0>(Gc, li, lk, acc[0]); \
+        if (NT > 1) hp_gram_store<R1, C1>(Gc, li, lk, acc[1]); \
+        if (NT > 2) hp_gram_store<R2, C2>(Gc, li, lk, acc[2]); }
+    GR_DEAL(sel, GR_OUT)
+#undef GR_OUT
     }   // cells
 }
+#undef GR_DEAL
 
 // (round 4: four entries per thread with all their loads in flight - with sixteen entries per thread taken one
 // after the other the kernel was sixteen memory latencies long, 11 us for a handful of cells)

@@ -2,6 +2,87 @@
 // hotpants -r / -rss of zuds/hotpants.py:42-44), one instance per kernel half width 1 .. 20.
 #include "hp_dev.h"
 
+// The accumulators of a pass leave its tap loop together.  Left alone, the compiler sinks each output's chain of
+// 2 HWK + 1 multiply-adds into the predicated block of that output's store: eight exec-mask branches, eight waits for
+// the whole window, and inside each block every multiply-add waits for the one before it.  An empty statement that
+// "modifies" all the values has to see them finished: the chains stay interleaved in front of it, tap by tap, and
+// only the stores behind it are predicated.
+static __device__ __forceinline__ void hv_pin(double (&a)[8]) {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
+}
+static __device__ __forceinline__ void hv_pin(double (&a)[5]) {
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]));
+}
+
+// Rows per work item of the y pass.  HV_R rows make 7 x 49 = 343 items of the benchmark's substamp (sw = 49): five
+// and a third of the workgroup's eight waves, two SIMDs with two busy waves and two with one, and the pass as long as
+// if all eight were busy.  Five rows make 10 x 49 = 490 items: all eight waves, 105 multiply-adds each instead of 168.
+// The short form is taken where the long one fills more than half the workgroup (a SIMD with two waves) and the short
+// one still fits one round; an output's sum is the same taps in the same order in both.
+#define HV_RY 5
+static __device__ __forceinline__ int hv_rows_y(int cwe, int sw) {
+    return (cwe * ((sw + HV_R - 1) / HV_R) > HV_THREADS / 2 && cwe * ((sw + HV_RY - 1) / HV_RY) <= HV_THREADS) ? HV_RY : HV_R;
+}
+
+// y pass of one term: W[i][j] = sum_m fy[2 HWK - m] xp[i + m][j], R rows per lane (xp has HV_R >= R zero rows below).
+// (a function of values, not a lambda: a closure takes the plan's address - see the chunk loop of hp_vectors_body)
+template <int HWK, int R, bool PIN>
+static __device__ __forceinline__ void hv_ypass(int tid, int cwe, int c0, int sw, const double* xp, int cw,
+                                             const double* __restrict__ fyv, double sc, bool sub0, bool first, bool mine,
+                                             double* w0, char* Xn) {
+    constexpr int STEP = 2 * HWK + 1, WIN = R + 2 * HWK;
+    const unsigned rowb = (unsigned)sw * (unsigned)sizeof(double);
+    const unsigned cwb = (unsigned)cw * (unsigned)sizeof(double);
+    const int nstrip = (sw + R - 1) / R;
+    for (int e = tid; e < cwe * nstrip; e += HV_THREADS) {
+        const int s = e / cwe, jl = e - s * cwe, j = c0 + jl;      // consecutive lanes = consecutive columns
+        const int i0 = s * R;
+        // (the lane's own part of an address is formed once and kept from the compiler, which otherwise
+        // multiplies (i0 + k) cw + jl out again for each of the window's rows and each of the outputs: what
+        // is added per row is uniform and stays on the scalar unit.  PIN: not in the column-chunked form and not
+        // above half width 15 - in k_hp_vectors_big<16> and k_hp_vectors<20> the compiler answers the hint with a
+        // stack frame of 36 bytes that no instruction touches, and no instance is to have one)
+        unsigned colb = (unsigned)(i0 * cw + jl) * (unsigned)sizeof(double);
+        if (PIN) asm volatile("" : "+v"(colb));
+        const char* col = reinterpret_cast<const char*>(xp) + colb;
+        double wv[WIN];
+#pragma unroll
+        for (int k = 0; k < WIN; ++k)                            // rows >= pw are zero
+            wv[k] = *reinterpret_cast<const double*>(col + (unsigned)k * cwb);
+        double acc[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) acc[q] = 0.0;
+#pragma unroll
+        for (int m = 0; m < STEP; ++m) {
+            const double cf = fyv[2 * HWK - m];
+#pragma unroll
+            for (int q = 0; q < R; ++q) acc[q] += cf * wv[q + m];
+        }
+        hv_pin(acc);
+        int k0 = i0 * sw + j;                       // the first output; the others follow one row apart
+        asm volatile("" : "+v"(k0));
+        const int nv = sw - i0;                     // rows of this strip inside the substamp
+        // term 0's vector is read for all the outputs at once, outside any per-pixel
+        // condition (rows beyond the stamp read a clamped, unused entry: the last row's)
+        double wsub[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) wsub[q] = 0.0;
+        if (sub0) {
+            const int klast = (sw - 1) * sw + j;
+#pragma unroll
+            for (int q = 0; q < R; ++q) wsub[q] = w0[min(k0 + q * sw, klast)];
+        }
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const double v = acc[q] * sc - wsub[q];
+            if (q < nv) {
+                if (first) w0[k0 + q * sw] = v;
+                if (mine) *reinterpret_cast<double*>(Xn + ((unsigned)k0 * (unsigned)sizeof(double) + q * rowb)) = v;
+            }
+        }
+    }
+}
+
 // BIG (round 5: half widths up to 20, substamps up to 60 - hotpants takes -r 2.5 SEEING, -rss 6 SEEING unclamped,
 // zuds/hotpants.py:42-44): where the x-filtered patch, term 0 and the template patch do not fit 160 KB of LDS
 // together, the x-filtered patch is built and consumed in chunks of `cwarg` substamp columns (a column's y pass
@@ -179,9 +260,12 @@ static __device__ __forceinline__ void hp_vectors_body(const hp_plan& P, const f
 #pragma unroll
                 for (int q = 0; q < HV_R; ++q) acc[q] += cf * wv[q + m];
             }
+            hv_pin(acc);
+            double* xo = xp + yy * cw + jl0;
+            const int nv = sw - j0;                     // outputs of this strip inside the substamp
 #pragma unroll
             for (int q = 0; q < HV_R; ++q)
-                if (j0 + q < sw) xp[yy * cw + jl0 + q] = acc[q];
+                if (q < nv) xo[q] = acc[q];
         }
         __syncthreads();
         for (int n = tn0; n < tn1; ++n) {
@@ -189,43 +273,14 @@ static __device__ __forceinline__ void hp_vectors_body(const hp_plan& P, const f
             const double* fyv = filt + P.tfy[n] * STEP;
             const double sc = P.tscale[n];
             const bool sub0 = n != 0 && P.tsub0[n] != 0;
-            // y pass: W[i][j] = sum_m fy[2 HWK - m] xp[i + m][j]
-            for (int e = tid; e < cwe * nstrip; e += HV_THREADS) {
-                const int s = e / cwe, jl = e - s * cwe, j = c0 + jl;      // consecutive lanes = consecutive columns
-                const int i0 = s * HV_R;
-                const double* col = xp + i0 * cw + jl;
-                double wv[WIN];
-#pragma unroll
-                for (int k = 0; k < WIN; ++k) wv[k] = col[k * cw];        // rows >= pw are zero
-                double acc[HV_R];
-#pragma unroll
-                for (int q = 0; q < HV_R; ++q) acc[q] = 0.0;
-#pragma unroll
-                for (int m = 0; m < STEP; ++m) {
-                    const double cf = fyv[2 * HWK - m];
-#pragma unroll
-                    for (int q = 0; q < HV_R; ++q) acc[q] += cf * wv[q + m];
-                }
-                // term 0's vector is read for all eight outputs at once, outside any per-pixel
-                // condition (rows beyond the stamp read a clamped, unused entry)
-                double wsub[HV_R];
-#pragma unroll
-                for (int q = 0; q < HV_R; ++q) wsub[q] = 0.0;
-                if (sub0) {
-#pragma unroll
-                    for (int q = 0; q < HV_R; ++q) wsub[q] = w0[min(i0 + q, sw - 1) * sw + j];
-                }
-#pragma unroll
-                for (int q = 0; q < HV_R; ++q) {
-                    const int i = i0 + q;
-                    const int k = i * sw + j;
-                    const double v = acc[q] * sc - wsub[q];
-                    if (i < sw) {
-                        if (n == 0) w0[k] = v;
-                        if (mine) Xc[(size_t)n * P.npixp + k] = v;
-                    }
-                }
-            }
+            // (the term's row of X: a uniform base, formed once per term on the scalar unit; the outputs of a lane are
+            // that base plus a 32-bit byte offset that grows by one row pitch)
+            char* Xn = reinterpret_cast<char*>(Xc + (size_t)n * P.npixp);
+            constexpr bool PIN = !BIG && HWK <= 15;
+            if (!BIG && hv_rows_y(cwe, sw) == HV_RY)
+                hv_ypass<HWK, HV_RY, PIN>(tid, cwe, c0, sw, xp, cw, fyv, sc, sub0, n == 0, mine, w0, Xn);
+            else
+                hv_ypass<HWK, HV_R, PIN>(tid, cwe, c0, sw, xp, cw, fyv, sc, sub0, n == 0, mine, w0, Xn);
             if (n == 0) __syncthreads();
         }
         __syncthreads();

@@ -159,3 +159,40 @@ def test_cuts_and_detections_read_a_wide_table_unchanged():
     cat.data = wide
     cat.image = object()
     assert len(z.Detection.from_catalog(cat, filter=False)) == n
+
+
+MASK_RULE = "mask='correct' needs columns='param': masking belongs to the second pass"
+BAD_OPTIONS = [        # (keywords, message of extract_options and SubtractionJob, message of sextractor._extract)
+    (dict(mask='correct'), MASK_RULE, MASK_RULE),
+    (dict(columns='wide'), "columns='wide': one of ('isophotal', 'param')", "columns='wide': 'isophotal' or 'param'"),
+    (dict(deblend=dict(nthresh=3)), 'deblend: nthresh=3 must be a power of two in 2 .. 64', None),
+    (dict(deblend=dict(mincont=2)), 'deblend: mincont=2.0 must lie in [0, 1]', None),
+    (dict(clean=dict(param=0)), 'clean: param=0.0 must be finite and lie in [0.1, 10]', None),
+    (dict(deblend=dict(levels=8)), "deblend: unknown keys ['levels'] (nthresh, mincont)", None),
+]
+
+
+class _Image:
+    header, header_comments, ismapped, basename = {}, {}, False, 'x.fits'
+
+
+@pytest.mark.parametrize('kw,message,object_layer', BAD_OPTIONS, ids=[repr(kw) for kw, _, _ in BAD_OPTIONS])
+def test_bad_options_raise_the_same_text_from_every_door(kw, message, object_layer):
+    """One bad option at a time through ``extract_options`` (and ``_split_params``, which the engine's calls go through),
+    the object layer (``sextractor._extract`` and, for the settings it takes, ``extraction_settings``) and
+    ``SubtractionJob(detect=True)``: the whole text of the ValueError, as it has read since each option arrived."""
+    e = ex()
+    sx = importlib.import_module('zuds-pipeline_amd.sextractor')
+    nightly = importlib.import_module('zuds-pipeline_amd.nightly')
+    call = dict(catalog_type='FITS_LDAC', weight=np.ones((4, 4)))
+    doors = [(lambda: e.extract_options(**kw), message),
+             (lambda: sx._extract(_Image(), call, np.zeros((4, 4), np.float32), None, **kw), object_layer or message),
+             (lambda: nightly.SubtractionJob({}, {}, detect=True, **kw), message)]
+    if 'deblend' in kw or 'clean' in kw:
+        doors.append((lambda: sx.extraction_settings(None, None, **kw), message))
+    else:
+        doors.append((lambda: e._split_params(kw.get('columns', 'isophotal'), {}, kw.get('mask')), message))
+    for door, text in doors:
+        with pytest.raises(ValueError) as err:
+            door()
+        assert str(err.value) == text

@@ -217,7 +217,7 @@ extern "C" void zm_clean_params_default(zm_clean_params* p) {
     p->param = 1.0;
 }
 
-static int cl_check(const zm_clean_params* clean) {
+int zm_cl_check(const zm_clean_params* clean) {
     ZM_CHECK(clean, "zm_extract_clean: null CLEAN parameters");
     ZM_CHECK(std::isfinite(clean->param) && clean->param >= 0.1 && clean->param <= 10.0,
              "zm_extract_clean: bad parameters (param %g: finite, in [0.1, 10])", clean->param);
@@ -287,7 +287,7 @@ extern "C" int zm_clean_decide(zm_ctx* ctx, int n, const zm_object* rows, const 
                                const float* mthresh, int minarea, const zm_clean_params* clean, int32_t* out_into,
                                int32_t* out_root) {
     ZM_CHECK(ctx && rows && fdflux && dthresh && mthresh, "zm_clean_decide: null argument");
-    ZM_TRY(cl_check(clean));
+    ZM_TRY(zm_cl_check(clean));
     ZM_CHECK(n >= 1 && n <= (1 << 24) && minarea >= 1, "zm_clean_decide: bad sizes (n %d: 1 .. 2^24; minarea %d)", n, minarea);
     for (int k = 0; k < n; ++k)
         ZM_CHECK(rows[k].number == k + 1 && rows[k].npix >= minarea && rows[k].first >= 0,
@@ -322,51 +322,14 @@ extern "C" int zm_extract_clean_stats(zm_ctx* ctx, int max_n, double* fdflux, fl
     return 0;
 }
 
-extern "C" int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
-                                    const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
-                                    const zm_extract_params* params, int max_objects, zm_object* out_rows,
-                                    int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
-                                    int* out_status, const zm_deblend_params* deblend, const zm_clean_params* clean,
-                                    int32_t* out_parent, int32_t* out_nmerged) {
-    ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
-    ZM_TRY(cl_check(clean));
-    if (deblend) ZM_TRY(zm_db_check(deblend));
-    ZM_HIP(hipSetDevice(ctx->device));
-    const int np = nx * ny;
-    const int cap = max_objects;
-    const int minarea = params->detect_minarea;
-    zm_ex_bufs b;
-    ctx->cl_npre = 0;
-    ZM_TRY(zm_ex_planes(ctx, nx, ny, segm_dev, filtered_dev, &b));
-    zm_ex_label(ctx, img, sigma, bad, nx, ny, params, &b);
-    zm_ex_count_roots(ctx, b.label, minarea, &b);
-    ZM_HIP(hipGetLastError());
+// The CLEAN stage of zm_ex_first_pass (extract.hip): b->label holds the n0 > 0 objects of the pass before (d_seg1, d_split:
+// what zm_db_split left, or nullptr where nothing was deblended).  Numbers and measures that pass in full, decides, and
+// where anything is absorbed numbers and measures again; rows, PARENT_NUMBER, NMERGED and the call's counts are final.
+int zm_cl_merge(zm_ctx* ctx, const float* img, const float* sigma, const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                const zm_extract_params* params, int cap, const zm_clean_params* clean, int n0, const zm_ex_bufs* b,
+                int* d_seg1, int* d_split, zm_object* out_rows, const zm_ex_outs* o, int32_t* out_parent, int32_t* out_nmerged) {
+    const int np = b->np, minarea = params->detect_minarea;
     int head[2] = {0, 0};
-    ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_status) *out_status = head[0];
-    *out_nfound = head[1];
-    *out_nwritten = 0;
-    ZM_CHECK(head[0] == 0, "zm_extract_clean: a label chain passed its bound of %d steps (status %d)", np, head[0]);
-    const int n1 = head[1];
-    int *d_seg1 = nullptr, *d_split = nullptr;
-    if (deblend && n1 > 0) {
-        ZM_TRY(zm_db_split(ctx, img, sigma, flag, nx, ny, params, deblend, n1, &b, &d_seg1, &d_split));
-        ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-        ZM_HIP(hipStreamSynchronize(ctx->stream));
-        if (out_status) *out_status = head[0];
-        *out_nfound = head[1];
-        ZM_CHECK(head[0] == 0, "zm_extract_clean: a loop passed its bound (status %d: 1 label chain, 2 deblending)", head[0]);
-    }
-    const int n0 = head[1];                              // the objects CLEAN works on: all of them, whatever cap is
-    if (n0 == 0) {                                       // nothing to clean: the empty map
-        int* d_obj = nullptr;
-        ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
-        zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
-        ZM_HIP(hipGetLastError());
-        ZM_HIP(hipStreamSynchronize(ctx->stream));
-        return 0;
-    }
     // the pass before in full: its map, its table and its rows
     int *d_seg0 = nullptr, *d_obj0 = nullptr;
     char* d_stats = nullptr;
@@ -375,12 +338,12 @@ extern "C" int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* 
     ZM_TRY(ctx->get("cl_stats", (size_t)n0 * 16, (void**)&d_stats));
     double* d_F = (double*)d_stats;
     float *d_T = (float*)(d_stats + (size_t)n0 * 8), *d_M = d_T + n0;
-    zm_ex_number(ctx, b.label, img, flag, nx, ny, params, n0, d_seg0, d_obj0, &b);
-    hipLaunchKernelGGL(k_cl_stats, dim3(n0), dim3(256), 0, ctx->stream, d_seg0, b.filt, sigma, nx, params->detect_thresh, d_obj0,
+    zm_ex_number(ctx, b->label, img, flag, nx, ny, params, n0, d_seg0, d_obj0, b);
+    hipLaunchKernelGGL(k_cl_stats, dim3(n0), dim3(256), 0, ctx->stream, d_seg0, b->filt, sigma, nx, params->detect_thresh, d_obj0,
                        n0, minarea, d_F, d_T, d_M);
     ZM_HIP(hipGetLastError());
     std::vector<zm_object> pre(n0);
-    ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n0, d_seg0, d_obj0, &b, pre.data()));
+    ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n0, d_seg0, d_obj0, b, pre.data()));
     ctx->cl_npre = n0;
     std::vector<double> hF(n0);
     std::vector<float> hT((size_t)n0 * 2);
@@ -389,15 +352,12 @@ extern "C" int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* 
     ZM_HIP(hipStreamSynchronize(ctx->stream));
     std::vector<int32_t> root(n0);
     int *d_root, *d_newfirst, *d_nmerged;
-    ZM_TRY(cl_decide(ctx, n0, pre.data(), hF.data(), hT.data(), hT.data() + n0, clean, b.small, nullptr, root.data(), &d_root,
+    ZM_TRY(cl_decide(ctx, n0, pre.data(), hF.data(), hT.data(), hT.data() + n0, clean, b->small, nullptr, root.data(), &d_root,
                      &d_newfirst, &d_nmerged));
-    ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_status) *out_status = head[0];
-    ZM_CHECK(head[0] == 0, "zm_extract_clean: a chain of absorptions passed its bound of %d steps (status %d)", n0, head[0]);
+    ZM_TRY(zm_ex_head(ctx, b, o, "a chain of absorptions", n0, head));    // (the count is still n0)
     int nabsorbed = 0;
     for (int k = 0; k < n0; ++k) nabsorbed += root[k] != k + 1;
-    if (!deblend) {                                      // PARENT_NUMBER: the NUMBER of the pass before; nothing was split
+    if (!d_seg1) {                                       // PARENT_NUMBER: the NUMBER of the pass before; nothing was split
         d_seg1 = d_seg0;
         ZM_TRY(ctx->get("db_split", (size_t)n0 * 4, (void**)&d_split));
         ZM_HIP(hipMemsetAsync(d_split, 0, (size_t)n0 * 4, ctx->stream));
@@ -406,26 +366,24 @@ extern "C" int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* 
     int n = 0;
     if (nabsorbed == 0) {
         // nothing is absorbed: the label plane is untouched, map and rows are those of the pass before
-        *out_nfound = n0;
+        *o->nfound = n0;
         n = n0 < cap ? n0 : cap;
-        *out_nwritten = n;
-        ZM_HIP(hipMemcpyAsync(b.seg, d_seg0, (size_t)np * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        *o->nwritten = n;
+        ZM_HIP(hipMemcpyAsync(b->seg, d_seg0, (size_t)np * 4, hipMemcpyDeviceToDevice, ctx->stream));
         if (n > 0) memcpy(out_rows, pre.data(), (size_t)n * sizeof(zm_object));
         d_obj = d_obj0;
     } else {
         hipLaunchKernelGGL(k_cl_relabel, dim3(zm_div_up(np, 256)), dim3(256), 0, ctx->stream, d_seg0, d_root, d_newfirst, np, n0,
-                           b.label);
-        ZM_TRY(zm_ex_recount(ctx, b.label, &b));
-        zm_ex_count_roots(ctx, b.label, minarea, &b);
+                           b->label);
+        ZM_TRY(zm_ex_recount(ctx, b->label, b));
+        zm_ex_count_roots(ctx, b->label, minarea, b);
         ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
-        zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
+        zm_ex_number(ctx, b->label, img, flag, nx, ny, params, cap, b->seg, d_obj, b);
         ZM_HIP(hipGetLastError());
-        ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-        ZM_HIP(hipStreamSynchronize(ctx->stream));
-        *out_nfound = head[1];
-        n = head[1] < cap ? head[1] : cap;
-        *out_nwritten = n;
-        if (n > 0) ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows));
+        // (no kernel since the last read takes the status word: this one cannot fail on it)
+        ZM_TRY(zm_ex_head(ctx, b, o, "a chain of absorptions", n0, head, cap));
+        n = *o->nwritten;
+        if (n > 0) ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b->seg, d_obj, b, out_rows));
     }
     if (n == 0) {
         ZM_HIP(hipStreamSynchronize(ctx->stream));
@@ -444,13 +402,27 @@ extern "C" int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* 
     return 0;
 }
 
+extern "C" int zm_extract_clean_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
+                                    const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                                    const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                                    int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
+                                    int* out_status, const zm_deblend_params* deblend, const zm_clean_params* clean,
+                                    int32_t* out_parent, int32_t* out_nmerged) {
+    ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
+    ZM_TRY(zm_cl_check(clean));
+    if (deblend) ZM_TRY(zm_db_check(deblend));
+    const zm_ex_outs o = {out_nwritten, out_nfound, out_status, "zm_extract_clean"};
+    return zm_ex_first_pass(ctx, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, out_rows, segm_dev, filtered_dev, &o,
+                            deblend, clean, out_parent, out_nmerged);
+}
+
 extern "C" int zm_extract_clean(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
                                 const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
                                 const zm_extract_params* params, int max_objects, zm_object* out_rows,
                                 int32_t* out_segm, float* out_filtered, int* out_nwritten, int* out_nfound,
                                 int* out_status, const zm_deblend_params* deblend, const zm_clean_params* clean,
                                 int32_t* out_parent, int32_t* out_nmerged) {
-    ZM_TRY(cl_check(clean));
+    ZM_TRY(zm_cl_check(clean));
     return zm_ex_host(ctx, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, out_rows, out_segm, out_filtered,
                       out_nwritten, out_nfound, out_status, deblend, out_parent, clean, out_nmerged);
 }

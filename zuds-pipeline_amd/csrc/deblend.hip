@@ -450,39 +450,9 @@ extern "C" int zm_extract_deblend_dev(zm_ctx* ctx, const float* img, const float
                                       int* out_status, const zm_deblend_params* deblend, int32_t* out_parent) {
     ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
     ZM_TRY(zm_db_check(deblend));
-    ZM_HIP(hipSetDevice(ctx->device));
-    const int np = nx * ny;
-    const int cap = max_objects;
-    const int minarea = params->detect_minarea;
-    zm_ex_bufs b;
-    ZM_TRY(zm_ex_planes(ctx, nx, ny, segm_dev, filtered_dev, &b));
-    zm_ex_label(ctx, img, sigma, bad, nx, ny, params, &b);
-    zm_ex_count_roots(ctx, b.label, minarea, &b);
-    ZM_HIP(hipGetLastError());
-    int head[2] = {0, 0};
-    ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_status) *out_status = head[0];
-    *out_nfound = head[1];
-    *out_nwritten = 0;
-    ZM_CHECK(head[0] == 0, "zm_extract_deblend: a label chain passed its bound of %d steps (status %d)", np, head[0]);
-    const int n1 = head[1];
-    int *d_seg1 = nullptr, *d_split = nullptr;
-    if (n1 > 0) ZM_TRY(zm_db_split(ctx, img, sigma, flag, nx, ny, params, deblend, n1, &b, &d_seg1, &d_split));
-    int* d_obj = nullptr;
-    ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
-    zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
-    ZM_HIP(hipGetLastError());
-    ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_status) *out_status = head[0];
-    *out_nfound = head[1];
-    ZM_CHECK(head[0] == 0, "zm_extract_deblend: a loop passed its bound (status %d: 1 label chain, 2 deblending)", head[0]);
-    const int n = head[1] < cap ? head[1] : cap;
-    *out_nwritten = n;
-    if (n == 0) return 0;
-    ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows));
-    return zm_db_parent(ctx, d_obj, n, d_seg1, d_split, out_rows, out_parent);
+    const zm_ex_outs o = {out_nwritten, out_nfound, out_status, "zm_extract_deblend"};
+    return zm_ex_first_pass(ctx, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, out_rows, segm_dev, filtered_dev, &o,
+                            deblend, nullptr, out_parent, nullptr);
 }
 
 extern "C" int zm_extract_deblend(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,

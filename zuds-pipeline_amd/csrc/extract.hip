@@ -547,7 +547,7 @@ static void ex_finish_row(zm_object* r, const int* o, const ex_meas& m, int numb
     r->x_world = r->y_world = NAN;
 }
 
-// The stages of zm_extract_dev, shared with the deblending entry point (deblend.hip; declared in zm_internal.h).
+// The stages of zm_ex_first_pass (declared in zm_internal.h; deblend.hip and clean.hip call them too).
 int zm_ex_check(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_extract_params* params,
                 int max_objects, const zm_object* out_rows, const int* out_nwritten, const int* out_nfound) {
     ZM_CHECK(ctx && img && sigma && params && out_nwritten && out_nfound, "zm_extract: null argument");
@@ -609,6 +609,20 @@ int zm_ex_recount(zm_ctx* ctx, const int* label, const zm_ex_bufs* b) {
 void zm_ex_count_roots(zm_ctx* ctx, const int* label, int minarea, const zm_ex_bufs* b) {
     hipLaunchKernelGGL(k_ex_scan1, dim3(b->nsb), dim3(256), 0, ctx->stream, label, b->cnt, b->np, minarea, b->small + 4);
     hipLaunchKernelGGL(k_ex_scan2, dim3(1), dim3(1024), 0, ctx->stream, b->small + 4, b->nsb, b->small + 1);
+}
+
+// Waits for the stream and reads the head: head[0] the status word, head[1] the number of objects, into the call's
+// out_status and out_nfound (cap >= 0: and min(objects, cap) into out_nwritten).  A status word that is set fails the call:
+// `what` passed its bound of `bound` steps (bound 0: a loop of either kind).
+int zm_ex_head(zm_ctx* ctx, const zm_ex_bufs* b, const zm_ex_outs* o, const char* what, int bound, int head[2], int cap) {
+    ZM_HIP(hipMemcpyAsync(head, b->small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    ZM_HIP(hipStreamSynchronize(ctx->stream));
+    if (o->status) *o->status = head[0];
+    *o->nfound = head[1];
+    if (cap >= 0) *o->nwritten = head[1] < cap ? head[1] : cap;
+    if (bound) ZM_CHECK(head[0] == 0, "%s: %s passed its bound of %d steps (status %d)", o->who, what, bound, head[0]);
+    ZM_CHECK(head[0] == 0, "%s: %s passed its bound (status %d: 1 label chain, 2 deblending)", o->who, what, head[0]);
+    return 0;
 }
 
 // numbering, segmentation map into `seg`, integer reductions into `obj` (cap rows)
@@ -673,33 +687,63 @@ int zm_ex_rows(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny
     return 0;
 }
 
+// The first pass of every form on device planes (checked by the caller): zm_extract_dev (deblend and clean NULL),
+// zm_extract_deblend_dev and zm_extract_clean_dev (clean set, deblend or not).  Only the forms that split or merge read the
+// head early: they need the objects of the pass before on the host.
+int zm_ex_first_pass(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* flag, int nx, int ny,
+                     const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                     int32_t* segm_dev, float* filtered_dev, const zm_ex_outs* o, const zm_deblend_params* deblend,
+                     const zm_clean_params* clean, int32_t* out_parent, int32_t* out_nmerged) {
+    ZM_HIP(hipSetDevice(ctx->device));
+    const int np = nx * ny, cap = max_objects;
+    zm_ex_bufs b;
+    int head[2] = {0, 0};
+    if (clean) ctx->cl_npre = 0;
+    // planes, labels, roots
+    ZM_TRY(zm_ex_planes(ctx, nx, ny, segm_dev, filtered_dev, &b));
+    zm_ex_label(ctx, img, sigma, bad, nx, ny, params, &b);
+    zm_ex_count_roots(ctx, b.label, params->detect_minarea, &b);
+    // split, merge
+    int *d_seg1 = nullptr, *d_split = nullptr;
+    if (deblend || clean) {
+        ZM_HIP(hipGetLastError());
+        ZM_TRY(zm_ex_head(ctx, &b, o, "a label chain", np, head, 0));
+        if (deblend && head[1] > 0) {
+            ZM_TRY(zm_db_split(ctx, img, sigma, flag, nx, ny, params, deblend, head[1], &b, &d_seg1, &d_split));
+            if (clean) ZM_TRY(zm_ex_head(ctx, &b, o, "a loop", 0, head));
+        }
+        if (clean && head[1] > 0)                        // it numbers and measures what it leaves
+            return zm_cl_merge(ctx, img, sigma, flag, nx, ny, wcs, params, cap, clean, head[1], &b, d_seg1, d_split, out_rows, o,
+                               out_parent, out_nmerged);
+    }
+    // number
+    int* d_obj = nullptr;
+    ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
+    zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
+    ZM_HIP(hipGetLastError());
+    if (clean) {                                         // nothing to clean: the empty map
+        ZM_HIP(hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
+    // head, rows, parent
+    if (deblend) ZM_TRY(zm_ex_head(ctx, &b, o, "a loop", 0, head));
+    else ZM_TRY(zm_ex_head(ctx, &b, o, "a label chain", np, head, cap));
+    const int n = head[1] < cap ? head[1] : cap;
+    *o->nwritten = n;
+    if (n == 0) return 0;
+    ZM_TRY(zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows));
+    return deblend ? zm_db_parent(ctx, d_obj, n, d_seg1, d_split, out_rows, out_parent) : 0;
+}
+
 extern "C" int zm_extract_dev(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad,
                               const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
                               const zm_extract_params* params, int max_objects, zm_object* out_rows,
                               int32_t* segm_dev, float* filtered_dev, int* out_nwritten, int* out_nfound,
                               int* out_status) {
     ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
-    ZM_HIP(hipSetDevice(ctx->device));
-    const int np = nx * ny;
-    const int cap = max_objects;
-    zm_ex_bufs b;
-    int* d_obj = nullptr;
-    ZM_TRY(zm_ex_planes(ctx, nx, ny, segm_dev, filtered_dev, &b));
-    ZM_TRY(ctx->get("ex_obj", (size_t)(cap + 1) * EX_OI * 4, (void**)&d_obj));
-    zm_ex_label(ctx, img, sigma, bad, nx, ny, params, &b);
-    zm_ex_count_roots(ctx, b.label, params->detect_minarea, &b);
-    zm_ex_number(ctx, b.label, img, flag, nx, ny, params, cap, b.seg, d_obj, &b);
-    ZM_HIP(hipGetLastError());
-    int head[2] = {0, 0};
-    ZM_HIP(hipMemcpyAsync(head, b.small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZM_HIP(hipStreamSynchronize(ctx->stream));
-    if (out_status) *out_status = head[0];
-    *out_nfound = head[1];
-    const int n = head[1] < cap ? head[1] : cap;
-    *out_nwritten = n;
-    ZM_CHECK(head[0] == 0, "zm_extract: a label chain passed its bound of %d steps (status %d)", np, head[0]);
-    if (n == 0) return 0;
-    return zm_ex_rows(ctx, img, sigma, nx, ny, wcs, params, n, b.seg, d_obj, &b, out_rows);
+    const zm_ex_outs o = {out_nwritten, out_nfound, out_status, "zm_extract"};
+    return zm_ex_first_pass(ctx, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, out_rows, segm_dev, filtered_dev, &o,
+                            nullptr, nullptr, nullptr, nullptr);
 }
 
 // host planes in, host planes out, for zm_extract (deblend == nullptr), zm_extract_deblend and zm_extract_clean (clean set)
@@ -707,10 +751,9 @@ int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
                const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows, int32_t* out_segm,
                float* out_filtered, int* out_nwritten, int* out_nfound, int* out_status, const zm_deblend_params* deblend,
                int32_t* out_parent, const zm_clean_params* clean, int32_t* out_nmerged) {
-    ZM_CHECK(ctx && img && sigma, "zm_extract: null argument");
-    // rows go on gridDim.y, four per workgroup of the filter: 65535 x 4 rows at the most
-    ZM_CHECK(nx > 0 && ny > 0 && (int64_t)nx * ny <= (int64_t)1 << 30 && ny <= 65535 * 4,
-             "zm_extract: bad sizes %d x %d (at most 2^30 pixels and 262140 rows)", nx, ny);
+    ZM_TRY(zm_ex_check(ctx, img, sigma, nx, ny, params, max_objects, out_rows, out_nwritten, out_nfound));
+    if (clean) ZM_TRY(zm_cl_check(clean));
+    if (deblend) ZM_TRY(zm_db_check(deblend));
     ZM_HIP(hipSetDevice(ctx->device));
     const size_t np = (size_t)nx * ny;
     float *d_img = nullptr, *d_sig = nullptr, *d_filt = nullptr;
@@ -731,13 +774,10 @@ int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
     ZM_TRY(ctx->get("ex_seg", np * 4, (void**)&d_seg));
     ZM_TRY(ctx->get("ex_filt", np * 4, (void**)&d_filt));
     int st = 0;
-    const int rc = clean   ? zm_extract_clean_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows,
-                                                  d_seg, d_filt, out_nwritten, out_nfound, &st, deblend, clean, out_parent,
-                                                  out_nmerged)
-                   : deblend ? zm_extract_deblend_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows,
-                                                    d_seg, d_filt, out_nwritten, out_nfound, &st, deblend, out_parent)
-                           : zm_extract_dev(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows, d_seg,
-                                            d_filt, out_nwritten, out_nfound, &st);
+    const zm_ex_outs o = {out_nwritten, out_nfound, &st,
+                          clean ? "zm_extract_clean" : deblend ? "zm_extract_deblend" : "zm_extract"};
+    const int rc = zm_ex_first_pass(ctx, d_img, d_sig, d_bad, d_flag, nx, ny, wcs, params, max_objects, out_rows, d_seg, d_filt,
+                                    &o, deblend, clean, out_parent, out_nmerged);
     if (out_status) *out_status = st;
     if (rc != 0 && st == 0) return rc;                   // with the status word set the planes still come back: they show where
     if (out_segm) ZM_HIP(hipMemcpyAsync(out_segm, d_seg, np * 4, hipMemcpyDeviceToHost, ctx->stream));

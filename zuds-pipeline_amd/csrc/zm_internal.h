@@ -243,7 +243,9 @@ int zm_launch_mask_finalize(zm_ctx* ctx, int32_t* acc, float* cov, int64_t npix)
 int zm_launch_split_pairs(zm_ctx* ctx, const float2* src, int64_t npix, float* a, float* b);
 int zm_launch_mask_widen(zm_ctx* ctx, const int16_t* in, int64_t n, int32_t* out);
 
-// ---- source extraction: the stages of zm_extract_dev (extract.hip), which zm_extract_deblend_dev (deblend.hip) reuses ----
+// ---- source extraction: zm_ex_first_pass (extract.hip) is the first pass of all three forms, zm_extract[_dev],
+// zm_extract_deblend[_dev] and zm_extract_clean[_dev]; the zm_ex_* stages (extract.hip) serve every form, zm_db_*
+// (deblend.hip) the deblending and the CLEAN form, zm_cl_merge (clean.hip) the CLEAN form alone ----
 #define EX_OI 8                      // ints per object: xmin, xmax, ymin, ymax, npix, flag OR, bits, root
 struct zm_ex_bufs {
     float* filt;                     // filtered plane
@@ -251,13 +253,22 @@ struct zm_ex_bufs {
     int* small;                      // [0] status word, [1] number of objects, [4 ..] block counts of the scan
     int np, nsb;
 };
+struct zm_ex_outs {                  // where a call reports: out_nwritten, out_nfound, out_status (or NULL) of the entry point
+    int *nwritten, *nfound, *status;
+    const char* who;                 // ... and its name, for the last-error text
+};
 int zm_ex_check(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_extract_params* params,
                 int max_objects, const zm_object* out_rows, const int* out_nwritten, const int* out_nfound);
+int zm_ex_first_pass(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, const int32_t* flag, int nx, int ny,
+                     const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows,
+                     int32_t* segm_dev, float* filtered_dev, const zm_ex_outs* o, const zm_deblend_params* deblend,
+                     const zm_clean_params* clean, int32_t* out_parent, int32_t* out_nmerged);
 int zm_ex_planes(zm_ctx* ctx, int nx, int ny, int32_t* segm_dev, float* filtered_dev, zm_ex_bufs* b);
 void zm_ex_label(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t* bad, int nx, int ny,
                  const zm_extract_params* params, const zm_ex_bufs* b);
 int zm_ex_recount(zm_ctx* ctx, const int* label, const zm_ex_bufs* b);
 void zm_ex_count_roots(zm_ctx* ctx, const int* label, int minarea, const zm_ex_bufs* b);
+int zm_ex_head(zm_ctx* ctx, const zm_ex_bufs* b, const zm_ex_outs* o, const char* what, int bound, int head[2], int cap = -1);
 void zm_ex_number(zm_ctx* ctx, const int* label, const float* img, const int32_t* flag, int nx, int ny,
                   const zm_extract_params* params, int cap, int* seg, int* obj, const zm_ex_bufs* b);
 int zm_ex_rows(zm_ctx* ctx, const float* img, const float* sigma, int nx, int ny, const zm_wcs* wcs,
@@ -267,10 +278,13 @@ int zm_ex_host(zm_ctx* ctx, const float* img, const float* sigma, const uint8_t*
                const zm_wcs* wcs, const zm_extract_params* params, int max_objects, zm_object* out_rows, int32_t* out_segm,
                float* out_filtered, int* out_nwritten, int* out_nfound, int* out_status, const zm_deblend_params* deblend,
                int32_t* out_parent, const zm_clean_params* clean = nullptr, int32_t* out_nmerged = nullptr);
-// the stages of zm_extract_deblend_dev (deblend.hip), which zm_extract_clean_dev (clean.hip) reuses
 int zm_db_check(const zm_deblend_params* deblend);
 int zm_db_split(zm_ctx* ctx, const float* img, const float* sigma, const int32_t* flag, int nx, int ny,
                 const zm_extract_params* params, const zm_deblend_params* deblend, int n1, const zm_ex_bufs* b, int** out_seg1,
                 int** out_split);
 int zm_db_parent(zm_ctx* ctx, const int* d_obj, int n, const int* d_seg1, const int* d_split, zm_object* out_rows,
                  int32_t* out_parent);
+int zm_cl_check(const zm_clean_params* clean);
+int zm_cl_merge(zm_ctx* ctx, const float* img, const float* sigma, const int32_t* flag, int nx, int ny, const zm_wcs* wcs,
+                const zm_extract_params* params, int cap, const zm_clean_params* clean, int n0, const zm_ex_bufs* b,
+                int* d_seg1, int* d_split, zm_object* out_rows, const zm_ex_outs* o, int32_t* out_parent, int32_t* out_nmerged);

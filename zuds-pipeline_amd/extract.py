@@ -172,13 +172,32 @@ def mask_params(mask, aper_radius=3.0):
     return p
 
 
-def with_column(tab, name, values):
-    """``tab`` with one more int32 column."""
-    out = np.zeros(len(tab), dtype=np.dtype(tab.dtype.descr + [(name, 'i4')]))
+def extract_options(columns='isophotal', deblend=False, clean=False, mask=None):
+    """The one place the options of an extraction are validated: (columns, ``deblend_settings(deblend)``,
+    ``clean_settings(clean)``, ``mask_setting(mask)``).  ``columns`` must be one of ``COLUMN_SETS`` and a mask needs the wide
+    table; anything else raises ValueError."""
+    if columns not in COLUMN_SETS:
+        raise ValueError(f'columns={columns!r}: one of {COLUMN_SETS}')
+    kind = mask_setting(mask)
+    if kind is not None and columns != 'param':
+        raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
+    return columns, deblend_settings(deblend), clean_settings(clean), kind
+
+
+def with_columns(tab, columns):
+    """``tab`` with more columns behind its own: ``columns`` is a list of (name, type, values); values beyond the table's
+    length are left out."""
+    out = np.zeros(len(tab), dtype=np.dtype(tab.dtype.descr + [(name, t) for name, t, _ in columns]))
     for c in tab.dtype.names:
         out[c] = tab[c]
-    out[name] = values[:len(tab)]
+    for name, _, values in columns:
+        out[name] = values[:len(tab)]
     return out.view(np.recarray)
+
+
+def with_column(tab, name, values):
+    """``tab`` with one more int32 column."""
+    return with_columns(tab, [(name, 'i4', values)])
 
 
 def with_parent(tab, parent):
@@ -189,13 +208,9 @@ def with_parent(tab, parent):
 def _split_params(columns, params, mask=None):
     """(extraction keywords, zm_measure_params or None, zm_mask_params or None) of a call's ``columns``, keyword
     arguments and ``mask``."""
-    if columns not in COLUMN_SETS:
-        raise ValueError(f'columns={columns!r}: one of {COLUMN_SETS}')
+    columns, _, _, kind = extract_options(columns, mask=mask)
     params = dict(params)
-    kind = mask_setting(mask)
     if columns != 'param':
-        if kind is not None:
-            raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
         return params, None, None
     mp = measure_params(params.pop('kron_fact', 2.5), params.pop('kron_min_radius', 3.5), params.get('filter', True))
     return params, mp, mask_params(kind, params.get('aper_radius', 3.0))
@@ -219,14 +234,10 @@ def masked_table(rows, ext, msk, n):
     ``MASK_COLUMNS`` are added.  Returns (table, ext rows, mask rows)."""
     wide, rext = ext_to_table(rows, ext, n)
     rmsk = np.frombuffer(msk, dtype=np.dtype(_lib.zm_object_mask), count=n) if n else np.zeros(0, np.dtype(_lib.zm_object_mask))
-    tab = np.zeros(n, dtype=np.dtype(wide.dtype.descr + [(c, t) for c, _, t in MASK_COLUMNS]))
-    for c in wide.dtype.names:
-        tab[c] = wide[c]
+    tab = with_columns(wide, [(col, t, rmsk[field]) for col, field, t in MASK_COLUMNS])
     tab['FLUX_APER'], tab['FLUXERR_APER'] = rmsk['flux_aper'], rmsk['fluxerr_aper']
     tab['FLAGS'] |= (rmsk['crowded'] != 0).astype(np.int32)
-    for col, field, _ in MASK_COLUMNS:
-        tab[col] = rmsk[field]
-    return tab.view(np.recarray), rext, rmsk.copy().view(np.recarray)
+    return tab, rext, rmsk.copy().view(np.recarray)
 
 
 def _measure(self, dev, img, sigma, bad, segm, nx, ny, wcs, mp, n, mk=None):
@@ -255,7 +266,15 @@ def rows_to_table(rows, n):
     return tab.view(np.recarray)
 
 
-def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, segm, filtered, deblend=None, clean=None):
+# (clean set, deblend set) -> the entry point of the first pass; the device-plane forms end in _dev
+ENTRY_POINTS = {(False, False): 'zm_extract', (False, True): 'zm_extract_deblend',
+                (True, False): 'zm_extract_clean', (True, True): 'zm_extract_clean'}
+
+
+def _call(self, dev, img, sigma, bad, flag, nx, ny, wcs, params, max_objects, segm, filtered, deblend=None, clean=None):
+    """The first pass: (table, number found, status word).  ``deblend`` / ``clean``: zm_deblend_params / zm_clean_params
+    or None; the deblending form takes two more arguments and gives one more column (PARENT_NUMBER), the CLEAN form takes
+    both parameter blocks and gives NMERGED always, PARENT_NUMBER only with deblending."""
     # the row array is kept between calls (12 MB at the default capacity: allocating and clearing it takes longer than
     # the extraction of a frame), one per calling thread: threads that share an engine do not share rows
     nrows = max(int(max_objects), 1)
@@ -265,26 +284,50 @@ def _call(self, fn, what, img, sigma, bad, flag, nx, ny, wcs, params, max_object
         rows = cache[threading.get_ident()] = (_lib.zm_object * nrows)()
     nw, nf, st = C.c_int(), C.c_int(), C.c_int()
     w = wcs_struct(wcs) if wcs is not None else None
-    if clean is not None:
-        # fn is the CLEAN form of the entry point: PARENT_NUMBER only with deblending, NMERGED always
-        parent, nmerged = np.zeros(nrows, np.int32), np.zeros(nrows, np.int32)
-        check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
-                 int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st),
-                 C.byref(deblend) if deblend is not None else None, C.byref(clean), ptr(parent), ptr(nmerged)), what)
-        tab = rows_to_table(rows, nw.value)
+    what = ENTRY_POINTS[clean is not None, deblend is not None] + ('_dev' if dev else '')
+    more, carried = [], []
+    if deblend is not None or clean is not None:
+        parent = np.zeros(nrows, np.int32)
+        more = [C.byref(deblend) if deblend is not None else None, ptr(parent)]
         if deblend is not None:
-            tab = with_parent(tab, parent)
-        return with_column(tab, 'NMERGED', nmerged), nf.value, st.value
-    if deblend is None:
-        check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
-                 int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st)), what)
-        return rows_to_table(rows, nw.value), nf.value, st.value
-    # fn is the deblending form of the entry point: two more arguments, one more column
-    parent = np.zeros(nrows, np.int32)
-    check(fn(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None, C.byref(params),
-             int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw), C.byref(nf), C.byref(st),
-             C.byref(deblend), ptr(parent)), what)
-    return with_parent(rows_to_table(rows, nw.value), parent), nf.value, st.value
+            carried.append(('PARENT_NUMBER', 'i4', parent))
+    if clean is not None:
+        nmerged = np.zeros(nrows, np.int32)
+        more = [more[0], C.byref(clean), more[1], ptr(nmerged)]
+        carried.append(('NMERGED', 'i4', nmerged))
+    check(getattr(self.L, what)(self._ctx, img, sigma, bad, flag, nx, ny, C.byref(w) if w is not None else None,
+                                C.byref(params), int(max_objects), C.cast(rows, C.c_void_p), segm, filtered, C.byref(nw),
+                                C.byref(nf), C.byref(st), *more), what)
+    tab = rows_to_table(rows, nw.value)
+    return (with_columns(tab, carried) if carried else tab), nf.value, st.value
+
+
+def _passes(self, dev, options, img, sigma, bad, flag, nx, ny, wcs, max_objects, segm, filtered):
+    """What ``Engine.extract`` (``dev`` False: host arrays as pointers) and ``Engine.extract_dev`` (device addresses) share:
+    the first pass, the second pass where ``columns='param'`` asked for one, and the columns of the first pass that the
+    wide table carries on.  ``options``: what ``_options`` returned.  Returns a dict with the keys of ``full=True`` but
+    the planes."""
+    p, mp, mk, db, cl = options
+    tab, nfound, status = _call(self, dev, img, sigma, bad, flag, nx, ny, wcs, p, max_objects, segm, filtered, db, cl)
+    out = dict(nfound=nfound, status=status)
+    if mp is not None:
+        first = tab
+        tab, out['ext'], maskrows = _measure(self, dev, img, sigma, bad, segm, nx, ny, wcs, mp, len(tab), mk)
+        if mk is not None:
+            out['maskrows'] = maskrows
+        carried = [(c, 'i4', first[c]) for c in ('PARENT_NUMBER', 'NMERGED') if c in first.dtype.names]
+        if carried:
+            tab = with_columns(tab, carried)
+    out['table'] = tab
+    return out
+
+
+def _options(columns, deblend, clean, mask, params):
+    """(zm_extract_params, zm_measure_params or None, zm_mask_params or None, zm_deblend_params or None, zm_clean_params or
+    None) of a call's keywords."""
+    params, mp, mk = _split_params(columns, params, mask)
+    db, cl = deblend_params(deblend), clean_params(clean)
+    return extract_params(**params), mp, mk, db, cl
 
 
 def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects=MAX_OBJECTS, full=False,
@@ -316,9 +359,7 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     FLUX_APER / FLUXERR_APER are then the masked values, FLAGS gains bit 1 where a tenth of a footprint was replaced or
     lost, the table gains ``MASK_COLUMNS``, and ``full=True`` adds ``maskrows`` (the zm_object_mask rows).  The map
     is the final one, after ``deblend`` and ``clean``."""
-    params, mp, mk = _split_params(columns, params, mask)
-    db = deblend_params(deblend)
-    cl = clean_params(clean)
+    options = _options(columns, deblend, clean, mask, params)
     img, sigma, flag = as_f32(img), as_f32(sigma), as_i32(flag)
     ny, nx = img.shape
     if sigma.shape != img.shape:
@@ -328,28 +369,13 @@ def _engine_extract(self, img, sigma, bad=None, flag=None, wcs=None, max_objects
     for a, nm in ((bad, 'bad'), (flag, 'flag')):
         if a is not None and a.shape != img.shape:
             raise ValueError(f'{nm} has shape {a.shape}, expected {img.shape}')
-    p = extract_params(**params)
     segm = np.empty((ny, nx), np.int32)
     filt = np.empty((ny, nx), np.float32) if full else None
-    fn, what = ((self.L.zm_extract_clean, 'zm_extract_clean') if cl is not None else
-                (self.L.zm_extract, 'zm_extract') if db is None else (self.L.zm_extract_deblend, 'zm_extract_deblend'))
-    tab, nfound, status = _call(self, fn, what, ptr(img), ptr(sigma), ptr(bad), ptr(flag), nx, ny,
-                                wcs, p, max_objects, ptr(segm), ptr(filt), db, cl)
-    ext = None
-    if mp is not None:
-        first = tab
-        tab, ext, maskrows = _measure(self, False, ptr(img), ptr(sigma), ptr(bad), ptr(segm), nx, ny, wcs, mp, len(tab), mk)
-        if db is not None:
-            tab = with_parent(tab, first['PARENT_NUMBER'])
-        if cl is not None:
-            tab = with_column(tab, 'NMERGED', first['NMERGED'])
-    if full and ext is not None and mk is not None:
-        return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext, maskrows=maskrows)
-    if full and ext is not None:
-        return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status, ext=ext)
+    out = _passes(self, False, options, ptr(img), ptr(sigma), ptr(bad), ptr(flag), nx, ny, wcs, max_objects, ptr(segm),
+                  ptr(filt))
     if full:
-        return dict(table=tab, segm=segm, filtered=filt, nfound=nfound, status=status)
-    return tab, segm
+        return dict(table=out.pop('table'), segm=segm, filtered=filt, **out)
+    return out['table'], segm
 
 
 def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objects=MAX_OBJECTS, segm=None,
@@ -358,30 +384,15 @@ def _engine_extract_dev(self, img, sigma, bad, flag, nx, ny, wcs=None, max_objec
     int32 device plane that takes the segmentation map, or None).  Returns (table, number found).
     ``columns='param'`` needs the segmentation map for its second pass: without ``segm`` a plane is allocated for the
     call.  ``deblend``, ``clean``, ``mask``: as for ``Engine.extract``."""
-    params, mp, mk = _split_params(columns, params, mask)
-    db = deblend_params(deblend)
-    cl = clean_params(clean)
+    options = _options(columns, deblend, clean, mask, params)
     own = None
-    if mp is not None and not segm:
+    if options[1] is not None and not segm:
         from . import hipmem
         own = hipmem.DeviceBuffer(int(nx) * int(ny) * 4)         # (freed when this call returns)
         segm = own.ptr
-    p = extract_params(**params)
-    fn, what = ((self.L.zm_extract_clean_dev, 'zm_extract_clean_dev') if cl is not None else
-                (self.L.zm_extract_dev, 'zm_extract_dev') if db is None else
-                (self.L.zm_extract_deblend_dev, 'zm_extract_deblend_dev'))
-    tab, nfound, _ = _call(self, fn, what, int(img), int(sigma), int(bad) if bad else None,
-                           int(flag) if flag else None, int(nx), int(ny), wcs, p, max_objects,
-                           int(segm) if segm else None, None, db, cl)
-    if mp is not None:
-        first = tab
-        tab, _, _ = _measure(self, True, int(img), int(sigma), int(bad) if bad else None, int(segm), int(nx), int(ny),
-                             wcs, mp, len(tab), mk)
-        if db is not None:
-            tab = with_parent(tab, first['PARENT_NUMBER'])
-        if cl is not None:
-            tab = with_column(tab, 'NMERGED', first['NMERGED'])
-    return tab, nfound
+    out = _passes(self, True, options, int(img), int(sigma), int(bad) if bad else None, int(flag) if flag else None,
+                  int(nx), int(ny), wcs, max_objects, int(segm) if segm else None, None)
+    return out['table'], out['nfound']
 
 
 def _engine_clean_stats(self):

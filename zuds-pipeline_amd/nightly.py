@@ -82,18 +82,13 @@ class SubtractionJob(object):
             raise ValueError('deblend needs detect')
         if clean and not detect:
             raise ValueError('clean needs detect')
-        from .extract import COLUMN_SETS, clean_settings, deblend_settings, mask_setting
-        if columns not in COLUMN_SETS:
-            raise ValueError(f'columns={columns!r}: one of {COLUMN_SETS}')
+        from .extract import extract_options, mask_setting
         if columns != 'isophotal' and not detect:
             raise ValueError('columns needs detect')
-        self.columns, self.mask = columns, mask_setting(mask)
-        if self.mask is not None and not detect:
+        if mask_setting(mask) is not None and not detect:
             raise ValueError('mask needs detect')
-        if self.mask is not None and columns != 'param':
-            raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
-        self.deblend = deblend_settings(deblend)         # (raises on settings the extractor refuses)
-        self.clean = clean_settings(clean)
+        # (raises on settings the extractor refuses)
+        self.columns, self.deblend, self.clean, self.mask = extract_options(columns, deblend, clean, mask)
         self.rb_model, self.fid, self.rb_cut = rb_model, fid, rb_cut
         self.sci, self.ref, self.radec = sci, ref, radec
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag

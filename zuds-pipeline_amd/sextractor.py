@@ -174,9 +174,8 @@ def _extract(image, call, sub, sextractor_kws, columns='isophotal', deblend=Fals
         second = {}
     else:
         raise ValueError(f"columns={columns!r}: 'isophotal' or 'param'")
-    from .extract import mask_setting
-    if mask_setting(mask) is not None and columns != 'param':
-        raise ValueError(f"mask={mask!r} needs columns='param': masking belongs to the second pass")
+    from .extract import extract_options
+    extract_options(columns, deblend, clean, mask)
     settings = extraction_settings(sextractor_kws, image.header, deblend=deblend, clean=clean, mask=mask)
     settings.update(second)
     mask = getattr(image, 'mask_image', None)

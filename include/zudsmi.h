@@ -1044,6 +1044,46 @@ int zm_psf_photometry_batch_dev(zm_ctx* ctx, int nimg, const zm_psf_image* image
                                 double* y_dev, double* flux_dev, double* err_dev, double* chi2_dev, double* sky_dev,
                                 double* cover_dev, int32_t* npix_dev, int32_t* flags_dev);
 
+/* ---- fake sources: PSF-model point sources added to resident planes (csrc/inject.hip; DESIGN.md "Fake sources") ---- */
+/* zm_inject_dev adds n fakes to img (ny x nx float32, device) and, optionally, their Poisson variance to rms.  The fake list
+ * x, y (0-based pixels), flux (data units) is HOST memory, as the stamp origins of zm_stamps_dev are; model is the device
+ * array of a PSF model as zm_psf_photometry_dev takes it, (2 half + 1)^2 doubles, 1 <= half <= ZM_PSF_HALF_MAX.
+ *
+ * Geometry: that of zm_psf_photometry.  ix = floor(x + 0.5), fx = x - ix in [-0.5, 0.5), the same in y.  The profile at
+ * pixel (ix + i, iy + j) is P_ij, the model interpolated at (i - fx, j - fy) with the six Lanczos-3 taps at offsets -2 .. 3
+ * scaled to unit sum (a fractional part of 0 is a delta); the model is 0 outside its samples.  The walk over the 6 x 6 taps
+ * is that of the fit, in its order: rows outer, ty[a] * (sum_b tx[b] * m), no contraction.  The box of a fake is |i|, |j| <=
+ * half + 3, clipped to the frame.
+ * Image: every box pixel inside the frame with v = flux * P_ij != 0 becomes (float)((double)img + v).  Pixels with v == 0
+ * are not written (a fake of flux 0 writes nothing); a pixel that is not written keeps its bytes, NaN payloads and -0.0
+ * included.  A pixel holding NaN or inf is written by the same formula and stays non-finite.
+ * Rms: with rms != NULL and gain > 0 the same pixels with v > 0 whose rms is finite and positive become
+ * (float)sqrt((double)rms * rms + v / gain); every other rms pixel keeps its bytes.  No noise realisation is drawn.
+ * Overlaps: the result is that of adding the fakes one at a time in index order, each addition rounded to float32 as
+ * above, the same bytes on every run, without float atomics: zm_inject_layers gives every fake layer = 1 + max(layer of
+ * every EARLIER fake whose box shares a pixel with its own, 0); two boxes share a pixel iff |ix_a - ix_b| <= 2 (half + 3)
+ * and the same in y; a fake whose x or y is not finite has layer 0 and shares nothing.  zm_inject_dev makes one launch per
+ * layer, in order, on the context's stream: within a layer no two fakes share a pixel, and of every overlapping pair the
+ * earlier index lies in an earlier layer.  Fakes kept 2 (half + 3) + 1 pixels apart make one layer.
+ * out_sum[s] (device, or NULL): flux * sum(P_ij) over the pixels written, fp64, reduced in a fixed order: the flux really
+ * deposited.  out_flags[s] (device): ZM_INJ_* below, exact.
+ * n == 0 returns at once.  half outside 1 .. ZM_PSF_HALF_MAX, a negative or non-finite gain or core_radius, or NULL where
+ * a pointer is required: an error, zm_last_error names the function.  zm_inject_dev only enqueues (one copy of the fake list
+ * and the per-layer work list, then the launches); zm_inject takes every array from the host - the planes staged as
+ * zm_psf_photometry stages them, written back in place - and waits.  zm_inject_layers is host only and touches no GPU. */
+#define ZM_INJ_CLIPPED 1      /* a box pixel lies off the frame */
+#define ZM_INJ_OUTSIDE 2      /* no box pixel lies inside (always with ZM_INJ_CLIPPED): nothing written, out_sum 0 */
+#define ZM_INJ_BAD 4          /* mask given: a box pixel inside the frame with (i - fx)^2 + (j - fy)^2 <= core_radius^2 has mask & bad_bits */
+#define ZM_INJ_NONFINITE 8    /* a written pixel held a value that is not finite */
+#define ZM_INJ_BADPOS 16      /* x, y or flux is not finite: nothing written, out_sum NaN */
+int zm_inject_dev(zm_ctx* ctx, float* img, float* rms, const int32_t* mask, int32_t bad_bits, int nx, int ny, int n,
+                  const double* x, const double* y, const double* flux, const double* model, int half, double gain,
+                  double core_radius, double* out_sum, int32_t* out_flags);
+int zm_inject(zm_ctx* ctx, float* img, float* rms, const int32_t* mask, int32_t bad_bits, int nx, int ny, int n,
+              const double* x, const double* y, const double* flux, const double* model, int half, double gain,
+              double core_radius, double* out_sum, int32_t* out_flags);
+int zm_inject_layers(int n, const double* x, const double* y, int half, int32_t* out_layer, int* out_nlayers);
+
 /* ---- alert packets: cone searches against a catalogue that stays in HBM -------- */
 /* The cone searches of the reference's xmatch() (zuds/crossmatch.py: the three nearest PS1 and LegacySurvey rows within
  * 30 arcsec, every ZTF alert, milliquas and TNS row within 1.5 arcsec) against local tables (csrc/skyindex.hip; DESIGN.md,

@@ -7,7 +7,7 @@ subtractions as one batch of launches on each of J lanes (``nightly.SubtractionP
 
 usage: donightly.py images.txt ref.fits [positions.txt] [--jobs J] [--fit-batch B] [--batch FRAMES] [--nreg-side N]
                     [--detect [--stamps] [--deblend] [--clean [--clean-param X]] [--rb-model BASE [--rb-cut X]] [--associate [--stars F]]]
-                    [--maglim]
+                    [--maglim] [--psf] [--fakes [N] [--fake-mags A,B] [--fake-seed S]]
 
 * ``images.txt``: science image paths (``*sciimg.fits``; the mask is ``*mskimg.fits``; a
   ``.weight.fits`` sibling is required: 1 / rms^2, 0 on bad pixels).  The list is sharded over
@@ -32,6 +32,13 @@ DESIGN.md "CLEAN"): the tables carry ``NMERGED`` and the headers say ``ZMCLEAN =
 ``--maglim``: every ``sub.*.fits`` gets a ``MAGLIM`` card, 5 sigma in an r = 3 px aperture, measured by the pool on the noise
 plane and mask in HBM (``SubtractionJob(maglim=True)`` -> ``DeviceSubtraction.maglim``) with ``MAGZP + APCOR4`` of the science
 header; a frame without those cards gets a warning and no card.
+``--psf``: the PSF model of every science frame is built from its own stars (``psf.build_psf_planes``; DESIGN.md, "PSF
+photometry"), written as ``<sci>.psf.fits`` and copied as ``sub.*.psf.fits``; its cards go into the subtraction's header.
+``--fakes [N]`` (needs ``--detect`` and a PSF model: ``--psf``, or an existing ``<sci>.psf.fits``): the detection efficiency
+of every subtraction is measured with N (200) fake sources (``SubtractionJob(fakes=...)`` -> ``fakes.recover_dev``; DESIGN.md,
+"Fake sources"): uniform in ``MAGLIM - 2.5 .. MAGLIM + 1`` of the science header (or ``--fake-mags A,B``), seed 0
+(``--fake-seed S``).  ``sub.*.fakes.csv`` is written and ``sub.*.fits`` gets ``FAKEN``, ``FAKESEED``, ``FAKEM50``, ``FAKEM80``.
+Such jobs run on per-job workers (``--fit-batch`` is ignored).  The other products are the same bytes.
 ``--associate`` (needs ``--detect``): once the pool has drained, the night's
 in-memory tables go through ``zuds.associate`` (the job of ``nersc/makesources.py``; ``scripts/makesources.py`` does the
 same from the ``sub.*.cat`` files) and ``<images>.sources.txt`` / ``<images>.sources.det.txt`` are written next to the
@@ -105,6 +112,20 @@ def load_science(io, fn):
     return sci
 
 
+def science_psf(io, fn, sci, build):
+    """The PSF model of a science frame: built from its own stars on the planes the ring decoded (``--psf``: the planes go
+    to the host once, ``psf.build_psf_planes``) and written as ``<sci>.psf.fits``, or read from that file."""
+    path = fn.replace('.fits', '.psf.fits')
+    if not build:
+        return zuds.PSFModel.from_file(path)
+    io.stream.synchronize()
+    sat = sci['header'].get('SATURATE')
+    res = zuds.psf.build_psf_planes(sci['img'].cpu().numpy(), mask=sci['mask'].cpu().numpy(), rms=sci['rms'].cpu().numpy(),
+                                    saturate=float(sat) if sat else None, engine=io.engine)
+    res['psf'].save(path)
+    return res['psf']
+
+
 def _load_dosub():
     """scripts/dosub.py as a module: it owns the layout of the stamps file and the guard MAX_DETS."""
     import importlib.util
@@ -162,7 +183,22 @@ def write_products(io, sci, ref, res):
             hdr['MAGLIM'] = float(ml['maglim'])
         else:
             print(f'{os.path.basename(out)}: no usable aperture on the noise plane, MAGLIM is not written', flush=True)
-    io.save(out, res['diff'], hdr)
+    model = sci.get('psf_built')
+    if model is not None:
+        # --psf: the science frame's model beside the subtraction, its cards in the header (as dosub.py --psf)
+        hdr.update(model.cards)
+        model.save(out.replace('.fits', '.psf.fits'))
+    if res.get('fakes_error'):
+        print(f'{os.path.basename(out)}: no efficiency from fakes: {res["fakes_error"]}', flush=True)
+    if res.get('fakes') is not None:
+        # --fakes: the matched table, and where the efficiency curve went
+        zuds.write_fakes_csv(out.replace('.fits', '.fakes.csv'), res['fakes'])
+        # (the cards go on the subtraction alone: its rms map and catalog keep the header of a run without --fakes)
+        fhdr = dict(hdr)
+        dosub.write_fake_cards(fhdr, None, sci['fake_settings'], res['efficiency'])
+        e = res['efficiency']
+        print(f'{os.path.basename(out)}: {int(e["nrec"].sum())} of {e["nused"]} fakes recovered, m50 {e["m50"]:.3f}', flush=True)
+    io.save(out, res['diff'], fhdr if res.get('fakes') is not None else hdr)
     io.save(out.replace('.fits', '.rms.fits'), res['noise'], hdr)
     mh = dict(sci['header'])
     mh['BIT17'] = 17
@@ -217,7 +253,21 @@ def main(argv=None):
     ap.add_argument('--maglim', action='store_true', help='write MAGLIM into sub.*.fits: 5 sigma in an r = 3 px aperture, from the '
                                                           'subtraction\'s own noise plane and the MAGZP / APCOR4 of the science '
                                                           'header (a frame without them: a warning, no card)')
+    ap.add_argument('--psf', action='store_true', help='build the PSF model of every science frame from its own stars: '
+                                                       '<sci>.psf.fits, sub.*.psf.fits and the PSF* cards of sub.*.fits')
+    ap.add_argument('--fakes', nargs='?', type=int, const=200, default=None, metavar='N',
+                    help='with --detect and a PSF model (--psf, or <sci>.psf.fits): the detection efficiency from N (200) fake '
+                         'sources; writes sub.*.fakes.csv and FAKEN / FAKESEED / FAKEM50 / FAKEM80')
+    ap.add_argument('--fake-mags', metavar='A,B', help='with --fakes: the magnitude range (default MAGLIM - 2.5 .. MAGLIM + 1)')
+    ap.add_argument('--fake-seed', metavar='S', help='with --fakes: the seed of the draw (default 0)')
     args = ap.parse_args(argv)
+    if (args.fakes is not None or args.fake_mags is not None or args.fake_seed is not None) and not args.detect:
+        print('--fakes needs --detect', file=sys.stderr)
+        return 2
+    fakes, err = dosub.check_fake_switches(args.fakes, args.fake_mags, args.fake_seed)      # (one validator for both drivers)
+    if err:
+        print(err, file=sys.stderr)
+        return 2
     if (args.associate or args.stars) and not (args.detect and (args.associate or not args.stars)):
         print('--associate needs --detect (and --stars needs --associate)', file=sys.stderr)
         return 2
@@ -246,11 +296,17 @@ def main(argv=None):
 
     nightly = importlib.import_module('zuds-pipeline_amd.nightly')
     device = importlib.import_module('zuds-pipeline_amd.device')
+    imgs = [str(f) for f in zuds.get_my_share_of_work(args.infile)]
+    if fakes and not args.psf:
+        missing = [fn for fn in imgs if not os.path.exists(fn.replace('.fits', '.psf.fits'))]
+        if missing:
+            print(f'--fakes needs a PSF model: --psf, or {os.path.basename(missing[0]).replace(".fits", ".psf.fits")} beside '
+                  f'the frame ({len(missing)} frame(s) without one)', file=sys.stderr)
+            return 2
     local = int(os.environ.get('LOCAL_RANK', '0'))
     import torch
     local %= max(torch.cuda.device_count(), 1)
     torch.cuda.set_device(local)
-    imgs = [str(f) for f in zuds.get_my_share_of_work(args.infile)]
     radec = None
     if args.positions:
         t = np.atleast_2d(np.loadtxt(args.positions))
@@ -258,14 +314,15 @@ def main(argv=None):
 
     io = device.FITSDeviceIO(local, engine=zuds.Engine(local))
     ref = load_reference(io, args.refname)
-    pool = nightly.SubtractionPool(args.jobs, device=local, batch=args.fit_batch)
+    # (a job with fakes runs on a per-job worker: SubtractionJob(fakes=...))
+    pool = nightly.SubtractionPool(args.jobs, device=local, batch=1 if fakes else args.fit_batch)
     ring = importlib.import_module('zuds-pipeline_amd.fitsring').FITSRing(local)
     rb_model = zuds.load_model(args.rb_model) if args.rb_model else None
     tables = [] if args.associate else None
     try:
         done = run_night(imgs, ref, pool, io, ring, radec, batch=args.batch, nreg_side=args.nreg_side,
                          detect=args.detect, stamps=args.stamps, rb_model=rb_model, rb_cut=args.rb_cut, tables=tables,
-                         deblend=args.deblend, clean=clean, maglim=args.maglim)
+                         deblend=args.deblend, clean=clean, maglim=args.maglim, psf=args.psf, fakes=fakes)
     finally:
         pool.close()
         ring.close()
@@ -291,7 +348,7 @@ def make_sources(tables, prefix, stars=None, engine=None):
 
 
 def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, detect=False, stamps=False, rb_model=None,
-              rb_cut=None, tables=None, deblend=False, clean=False, maglim=False):
+              rb_cut=None, tables=None, deblend=False, clean=False, maglim=False, psf=False, fakes=None):
     """The images of this rank against one reference.  The files of batch b + 1 are read, sent and decoded by the
     ring (fitsring.FITSRing: reader threads, copy stream) while the pool subtracts batch b; the products of batch b
     are encoded on the device, copied back on a third stream and written by the ring's writer threads while
@@ -351,9 +408,22 @@ def run_night(imgs, ref, pool, io, ring, radec=None, batch=36, nreg_side=3, dete
                 if rb_model is not None:
                     # the filter id as image.py reads it; a frame without the card and no --rb-cut fails here (ValueError)
                     rbkw = dict(rb_model=rb_model, rb_cut=rb_cut, fid=hdr.get('FID', hdr.get('FILTERID')))
+                if psf or fakes:
+                    sci_model = science_psf(io, fn, sci, build=psf)
+                    if psf:
+                        sci['psf_built'] = sci_model
+                if fakes:
+                    if 'MAGZP' not in hdr or 'PSFCOR' not in sci_model.cards:
+                        raise RuntimeError(f'{fn}: no MAGZP / PSFCOR: the fakes would have no zero point')
+                    spec = dict(psf=sci_model, zp=float(hdr['MAGZP']) + float(sci_model.cards['PSFCOR']), N=fakes['n'],
+                                SEED=fakes['seed'])
+                    if fakes.get('mags'):
+                        spec.update(MAG_MIN=fakes['mags'][0], MAG_MAX=fakes['mags'][1])
+                    rbkw['fakes'] = spec
                 job = nightly.SubtractionJob(sci, ref, radec=radec, nreg_side=nreg_side, tag=fn, detect=detect,
                                              stamps=stamps, max_detections=MAX_DETS, deblend=deblend, clean=clean, maglim=maglim,
                                              **rbkw)
+                sci['fake_settings'] = job.fake_settings
             except Exception:
                 # (the reference's drivers: try / except per image, scripts/dosub.py:205-213)
                 traceback.print_exception(*sys.exc_info())

@@ -5,6 +5,7 @@
 usage: dosub.py images.txt ref.fits [--detect [--stamps] [--param-columns [--mask-type blank|correct]] [--deblend]
                                         [--clean [--clean-param X]]
                                         [--rb-model BASE [--rb-cut X]]] [--maglim] [--psf [--psfref stars.cat]]
+                                        [--fakes [N] [--fake-mags A,B] [--fake-seed S]]
 images.txt lists science image paths (masks as ``*mskimg.fits``; a ``.weight.fits``
 or ``.rms.fits`` sibling is used when present, else the mesh background RMS map).
 ``ref.fits`` needs ``ref.mask.fits`` and ``ref.weight.fits`` next to it.
@@ -16,6 +17,14 @@ stars of a FITS_LDAC catalogue (``CalibratedImage.build_psf``; DESIGN.md, "PSF p
 ``<sci>.psf.fits`` and - the difference image has the science frame's PSF - copied as ``sub.*.psf.fits``; its cards
 (``PSFCOR``, ``PSFCORUN``, ``PSFNSTAR``, ``PSFHALF``, ``PSFFITR``, ``PSFFWHM``, ``ZMPSF``) go into the subtraction's header.
 ``dophot.py --psf`` reads the model beside each subtraction.  Without ``--psf`` nothing changes.
+With ``--fakes [N]`` (needs ``--detect`` and a PSF model: ``--psf``, or an existing ``<sci>.psf.fits``) the detection
+efficiency of every subtraction is measured with N (200) fake sources (``fakes.py``; DESIGN.md, "Fake sources"): they are
+drawn away from the subtraction's own detections, uniform in ``MAGLIM - 2.5 .. MAGLIM + 1`` of the science header (or
+``--fake-mags A,B``; a science frame without the card needs the switch) with
+seed 0 (``--fake-seed S``), added to a copy of the science frame with its PSF model at their sub-pixel phase, and the copy
+goes through the same subtraction, extraction and cuts in a temporary directory that is removed.  The table is written as
+``sub.*.fakes.csv`` and the subtraction's header gets ``FAKEN``, ``FAKESEED``, ``FAKEM50`` and ``FAKEM80`` (the magnitudes
+of 50 % and 80 % efficiency, when the curve crosses them).  The real products are not touched otherwise.
 With ``--detect`` every subtraction also gets its detection catalog (``sub.*.cat``, FITS_LDAC) and its filtered
 detections (``PipelineFITSCatalog.from_image`` -> ``Detection.from_catalog``, dosub.py:109-131).
 With ``--param-columns`` (needs ``--detect``) the catalog holds every column of ``sextractor.param`` (``MAG_AUTO``,
@@ -41,7 +50,9 @@ With ``--rb-model BASE`` (needs ``--detect``) the filter ends with the real / bo
 without that card and no ``--rb-cut`` is an error.
 """
 import os
+import shutil
 import sys
+import tempfile
 import time
 import traceback
 
@@ -92,8 +103,119 @@ def write_stamps(sub, detections, stamps, size=None):
                               [d.dec for d in detections], x0, y0, trimmed)
 
 
+def fake_run(sci, sub, ref, cat, model, fakes, sciclass, subclass, tmpdir, catkw, rb_model=None, rb_cut=None):
+    """``--fakes``: fake sources on a copy of ``sci`` through the same subtraction, extraction and cuts, in a temporary
+    directory under ``tmpdir`` that is removed.  ``cat``: the filtered catalog of the real run (the fakes avoid its
+    ``GOODCUT`` rows); ``model``: the PSF model; ``fakes``: dict(n=, seed=, mags=None | (a, b)); without ``mags`` the range
+    comes from the ``MAGLIM`` card of the SCIENCE header, as in ``donightly.py`` (not from the card ``--maglim`` writes on the
+    subtraction).  The copy always carries its noise as an rms map - the science frame's rms plane with the fakes' variance
+    added - also when the real run read ``<sci>.weight.fits``: the two maps mark bad pixels differently, so a fake run of
+    zero flux is not promised to reproduce the real run bit for bit here, as it is on the device route
+    (``fakes.recover_dev``).  Writes ``sub.*.fakes.csv`` and the ``FAKE*`` cards; returns (matched table, efficiency)."""
+    fk = zuds.fakes
+    if model is None:
+        raise RuntimeError(f'--fakes: {sci.basename} has no PSF model beside it')
+    cor = model.cards.get('PSFCOR', sci.header.get('PSFCOR'))
+    if cor is None or 'MAGZP' not in sci.header:
+        raise RuntimeError(f'"{sci.basename}" has no MAGZP / PSFCOR: the fakes would have no zero point')
+    kws = dict(N=fakes['n'], SEED=fakes['seed'])
+    if fakes.get('mags'):
+        kws.update(MAG_MIN=fakes['mags'][0], MAG_MAX=fakes['mags'][1])
+    st = fk.fake_settings(kws, header=sci.header, psf=model)
+    good = cat.data[cat.data['GOODCUT'] == 1]
+    table = fk.draw_fakes(sci.data.shape, sci.wcs, float(sci.header['MAGZP']) + float(cor), st,
+                          avoid_xy=(good['X_IMAGE'] - 1.0, good['Y_IMAGE'] - 1.0))
+    inj = fk.inject(sci, table, model, gain=st['gain'], core_radius=st['core_radius'])
+    with tempfile.TemporaryDirectory(dir=tmpdir, prefix='zmfakes') as d:
+        fn = os.path.join(d, os.path.basename(sci.local_path))
+        maskname = fn.replace('sciimg', 'mskimg') if 'sciimg' in fn else fn.replace('.fits', '.mask.fits')
+        zuds.fits.write(fn, inj['img'], dict(sci.header), dict(sci.header_comments or {}))
+        zuds.fits.write(fn.replace('.fits', '.rms.fits'), inj['rms'], dict(sci.header), dict(sci.header_comments or {}))
+        shutil.copyfile(sci.mask_image.local_path, maskname)
+        fsci = sciclass.from_file(fn)
+        fsci.mask_image = zuds.MaskImage.from_file(maskname)
+        fsci._rmsimg = zuds.FITSImage.from_file(fn.replace('.fits', '.rms.fits'))
+        fsub = subclass.from_images(fsci, ref, data_product=False, tmpdir=d, refined=True)
+        fcat = zuds.PipelineFITSCatalog.from_image(fsub, tmpdir=d, **catkw)
+        zuds.Detection.from_catalog(fcat, filter=True, rb_model=rb_model, rb_cut=rb_cut)
+        table = fk._append_columns(table, [('flux_in', 'f8', inj['flux_in']), ('inj_flags', 'i4', inj['inj_flags'])])
+        matched = fk.match_fakes(table, fcat.data, sci.wcs, st['match_radius'])
+    eff = fk.efficiency(matched)
+    fk.write_fakes_csv(sub.local_path.replace('.fits', '.fakes.csv'), matched)
+    write_fake_cards(sub.header, sub.header_comments, st, eff)
+    if sub.ismapped:
+        sub.save()
+    return matched, eff
+
+
+def write_fake_cards(header, comments, settings, eff):
+    """``FAKEN``, ``FAKESEED`` and - where the efficiency curve crosses them - ``FAKEM50`` / ``FAKEM80`` into a header."""
+    cards = {'FAKEN': int(eff['nused']), 'FAKESEED': int(settings['seed'])}
+    for key, name in (('FAKEM50', 'm50'), ('FAKEM80', 'm80')):
+        if eff[name] == eff[name]:                       # (a NaN has no place in a FITS card)
+            cards[key] = float(eff[name])
+    for key, value in cards.items():
+        header[key] = value
+        if comments is not None:
+            comments[key] = zuds.fakes.CARD_COMMENTS[key]
+    return cards
+
+
+def check_fake_switches(n, mags, seed):
+    """What ``--fakes [N]``, ``--fake-mags A,B`` and ``--fake-seed S`` say, for this driver and for ``donightly.py``: ``n``
+    is None without ``--fakes``, ``mags`` and ``seed`` are the texts given or None.  Returns (None | dict(n=, seed=, mags=),
+    None | an error message)."""
+    for flag, value in (('--fake-mags', mags), ('--fake-seed', seed)):
+        if value is not None and n is None:
+            return None, f'{flag} needs --fakes'
+    if n is None:
+        return None, None
+    if n < 1:
+        return None, f'--fakes: N must be positive (got {n})'
+    fakes = dict(n=int(n), seed=0, mags=None)
+    if seed is not None:
+        try:
+            fakes['seed'] = int(seed)
+            if fakes['seed'] < 0:
+                raise ValueError
+        except ValueError:
+            return None, f'--fake-seed: {seed!r} is not a seed'
+    if mags is not None:
+        try:
+            a, b = (float(t) for t in str(mags).split(','))
+            if not a <= b:
+                raise ValueError
+        except ValueError:
+            return None, f'--fake-mags: {mags!r} is not two ascending magnitudes A,B'
+        fakes['mags'] = (a, b)
+    return fakes, None
+
+
+def parse_fake_switches(argv):
+    """``--fakes [N] [--fake-mags A,B] [--fake-seed S]`` out of ``argv`` (a list, edited in place), through
+    ``check_fake_switches``."""
+    n = None
+    if '--fakes' in argv:
+        k = argv.index('--fakes')
+        n = 200
+        if k + 1 < len(argv) and argv[k + 1].lstrip('-').isdigit():
+            n = int(argv[k + 1])
+            del argv[k + 1]
+        del argv[k]
+    given = {}
+    for flag in ('--fake-mags', '--fake-seed'):
+        if flag not in argv:
+            continue
+        k = argv.index(flag)
+        if k + 1 >= len(argv):
+            return None, f'{flag} needs a value'
+        given[flag] = argv[k + 1]
+        del argv[k:k + 2]
+    return check_fake_switches(n, given.get('--fake-mags'), given.get('--fake-seed'))
+
+
 def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=False, param_columns=False, rb_model=None,
-           rb_cut=None, deblend=False, clean=False, mask=None, maglim=False, psf=False, psfref=None):
+           rb_cut=None, deblend=False, clean=False, mask=None, maglim=False, psf=False, psfref=None, fakes=None):
     tstart = time.time()
     sstart = time.time()
     sci = sciclass.from_file(fn)
@@ -170,6 +292,19 @@ def do_one(fn, sciclass, subclass, refname, tmpdir='/tmp', detect=False, stamps=
                                               f'on "{sub.basename}", something wrong with the image probably')
         dstop = time.time()
         print(f'det: {dstop - dstart:.2f} sec to make detections for {sub.basename}', flush=True)
+        if fakes:
+            fstart = time.time()
+            model = sub.psf_model if psf else sci.psf_model
+            try:
+                _, eff = fake_run(sci, sub, ref, cat, model, fakes, sciclass, subclass, tmpdir,
+                                  dict(columns='param' if param_columns else 'isophotal', deblend=deblend, clean=clean, mask=mask),
+                                  rb_model=rb_model, rb_cut=rb_cut)
+                print(f'fakes: {time.time() - fstart:.2f} sec for {eff["nused"]} fakes on {sub.basename}: '
+                      f'{int(eff["nrec"].sum())} recovered, m50 {eff["m50"]:.3f}', flush=True)
+            except Exception:
+                # the fake run is an extra: the frame keeps its products, its detections and its stamps
+                traceback.print_exception(*sys.exc_info())
+                print(f'fakes: no efficiency for {sub.basename}', flush=True)
 
     thumbs = None
     if detect and stamps:
@@ -204,6 +339,9 @@ def main(argv):
     if param_columns and not detect:
         print('--param-columns needs --detect', file=sys.stderr)
         return 2
+    if any(a in argv for a in ('--fakes', '--fake-mags', '--fake-seed')) and not detect:
+        print('--fakes needs --detect', file=sys.stderr)
+        return 2
     deblend = '--deblend' in argv
     if deblend and not detect:
         print('--deblend needs --detect', file=sys.stderr)
@@ -216,6 +354,10 @@ def main(argv):
         print('--clean-param needs --clean', file=sys.stderr)
         return 2
     argv = list(argv)
+    fakes, err = parse_fake_switches(argv)
+    if err:
+        print(err, file=sys.stderr)
+        return 2
     rb_model = rb_cut = mask = psfref = None
     for flag in ('--rb-model', '--rb-cut', '--clean-param', '--mask-type', '--psfref'):
         if flag in argv:
@@ -262,10 +404,17 @@ def main(argv):
     subclass = zuds.SingleEpochSubtraction
     sciclass = zuds.ScienceImage
     imgs = zuds.get_my_share_of_work(infile)
+    if fakes and not psf:
+        missing = [str(fn) for fn in imgs if not os.path.exists(str(fn).replace('.fits', '.psf.fits'))]
+        if missing:
+            print(f'--fakes needs a PSF model: --psf, or {os.path.basename(missing[0]).replace(".fits", ".psf.fits")} beside '
+                  f'the frame ({len(missing)} frame(s) without one)', file=sys.stderr)
+            return 2
     for fn in imgs:
         try:
             do_one(str(fn), sciclass, subclass, refname, detect=detect, stamps=stamps, param_columns=param_columns,
-                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask, maglim=maglim, psf=psf, psfref=psfref)
+                   rb_model=rb_model, rb_cut=rb_cut, deblend=deblend, clean=clean, mask=mask, maglim=maglim, psf=psf, psfref=psfref,
+                   fakes=fakes)
         except Exception:
             traceback.print_exception(*sys.exc_info())
             continue

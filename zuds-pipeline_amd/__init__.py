@@ -38,7 +38,8 @@ from .alert import *
 from .scamp import *
 from .photcal import *
 from .psf import *
-from . import synth, fits, scamp, lightcurve, photcal, psf
+from .fakes import *
+from . import synth, fits, scamp, lightcurve, photcal, psf, fakes
 
 # same DB-free entry points as the reference
 def init_db(*args, **kwargs):

@@ -207,6 +207,7 @@ GROWTH_BAD, GROWTH_SATURATED, GROWTH_NONFINITE, GROWTH_BOXCLIP, GROWTH_ANNCLIP, 
 PSF_HALF_MAX = 15                                      # ZM_PSF_HALF_MAX
 PSF_BAD, PSF_NONFINITE, PSF_BADRMS, PSF_CLIPPED, PSF_LOWCOVER, PSF_SINGULAR, PSF_BADPOS = \
     1, 2, 4, 8, 16, 32, 64                             # flags of zm_psf_photometry (ZM_PSF_*)
+INJ_CLIPPED, INJ_OUTSIDE, INJ_BAD, INJ_NONFINITE, INJ_BADPOS = 1, 2, 4, 8, 16      # flags of zm_inject (ZM_INJ_*)
 HP_UNSOLVED, HP_TIMEOUT, HP_PENDING = 1, 2, 4         # zm_hp_info.status bits (include/zudsmi.h)
 
 
@@ -325,6 +326,11 @@ _SIGS = {
                                         C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     'zm_psf_photometry_batch_dev': (C.c_int, [_P, C.c_int, C.POINTER(zm_psf_image), _P, _P, C.c_int64, C.c_int, _P, _P,
                                               C.c_int32, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'zm_inject_dev': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double,
+                                C.c_double, _P, _P]),
+    'zm_inject': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double,
+                            C.c_double, _P, _P]),
+    'zm_inject_layers': (C.c_int, [C.c_int, _P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
     'zm_extract_params_default': (None, [C.POINTER(zm_extract_params)]),
     'zm_extract_dev': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(zm_wcs), C.POINTER(zm_extract_params),
                                  C.c_int, _P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -66,11 +66,22 @@ class SubtractionJob(object):
     ``DeviceSubtraction.candidates``; the result then carries ``mask``.
     ``maglim``: the result also carries ``maglim``, the dict of ``DeviceSubtraction.maglim`` on the resident noise plane
     and mask with the zero point ``MAGZP + APCOR4`` of ``sci['header']``; a frame without those cards gets a warning and
-    no ``maglim``.  The three doubles cross to the host, so this waits for the chain."""
+    no ``maglim``.  The three doubles cross to the host, so this waits for the chain.
+    ``fakes`` (with ``detect``): None or dict(psf=PSFModel, zp=float, **fake_kws) - ``zp`` = ``MAGZP + PSFCOR``, the other
+    keys those of ``fakes.fake_settings`` (``N``, ``MAG_MIN``, ``MAG_MAX``, ``SEED``, ...; ``MAGLIM`` and ``GAIN`` of
+    ``sci['header']`` give their defaults).  The job is run and collected exactly as without ``fakes``; behind it the worker
+    runs ``fakes.recover_dev`` on the same chain - fake sources on a copy of the science frame, the same subtraction, the
+    same ``candidates`` settings - and the result also carries ``fakes`` (the matched table) and ``efficiency``
+    (``fakes.efficiency`` of it).  Every other entry of the result is the same bytes.  Fakes avoid the job's own ``GOODCUT``
+    detections.  With ``rb_model`` the fake run's stamps are cut from the frame that holds the fakes.  A fake pass that
+    fails - no room for ``N`` fakes, a library error, a stamp off the reference's grid - costs the job nothing: ``fakes``
+    and ``efficiency`` are None and ``fakes_error`` says why.  A pool with batched lanes refuses such a job with
+    ``ValueError``: ``SubtractionPool(batch >= 2)``, and a pool left at ``batch=0`` with ``njobs >= 6``, which batches of
+    its own accord; ``SubtractionPool(njobs, batch=1)`` runs it."""
 
     def __init__(self, sci, ref, radec=None, nreg_side=3, hotpants_kws=None, tag=None, detect=False, stamps=False,
                  max_detections=50, rb_model=None, fid=None, rb_cut=None, deblend=False, clean=False,
-                 columns='isophotal', mask=None, maglim=False):
+                 columns='isophotal', mask=None, maglim=False, fakes=None):
         if stamps and not detect:
             raise ValueError('stamps needs detect')
         if rb_model is not None:
@@ -94,6 +105,24 @@ class SubtractionJob(object):
         self.nreg_side, self.hotpants_kws, self.tag = nreg_side, hotpants_kws, tag
         self.detect, self.stamps, self.max_detections = bool(detect), bool(stamps), int(max_detections)
         self.maglim = bool(maglim)
+        self.fakes = self.fake_settings = None
+        if fakes is not None:
+            from .fakes import fake_settings
+            from .psf import PSFModel
+            if not detect:
+                raise ValueError('fakes needs detect')
+            if not isinstance(fakes, dict) or not isinstance(fakes.get('psf'), PSFModel):
+                raise ValueError('fakes must be a dict with psf, a PSFModel')
+            try:
+                zp = float(fakes['zp'])
+            except (KeyError, TypeError, ValueError):
+                raise ValueError('fakes needs zp, the zero point MAGZP + PSFCOR')
+            if not np.isfinite(zp):
+                raise ValueError(f'fakes: zp {zp!r} is not finite')
+            kws = {k: v for k, v in fakes.items() if k not in ('psf', 'zp')}
+            # (raises on an unknown key, or a magnitude range that nothing gives)
+            self.fake_settings = fake_settings(kws, header=sci.get('header'), psf=fakes['psf'])
+            self.fakes = dict(psf=fakes['psf'], zp=zp)
 
 
 class _Worker(object):
@@ -143,7 +172,15 @@ class _Worker(object):
         self.stream.synchronize()
         info = ch.result()
         out['info'] = {k: getattr(info, k) for k, _ in info._fields_}
-        return _settle(out)
+        out = _settle(out)
+        if getattr(job, 'fakes', None) is not None:
+            # behind the real job, whose results `out` already holds: what the fake pass raises is its own to carry, as
+            # the detection step's is (_detect)
+            try:
+                _fakes(ch, job, out)
+            except (_lib.ZMError, RuntimeError, ValueError) as exc:
+                out['fakes'], out['efficiency'], out['fakes_error'] = None, None, str(exc)
+        return out
 
 
 def _collect(w, ch, job, info, diff, noise, mask, keep):
@@ -238,6 +275,36 @@ def _detect(ch, job, out):
         out['stamps_error'] = str(exc)
         return
     out['stamps'] = dict(blocks=blocks, norms=norms, x0=x0, y0=y0, ra=ra, dec=dec)
+
+
+def _fakes(ch, job, out):
+    """The recovery pass of a job (``SubtractionJob(fakes=...)``), behind the job's own run, whose results ``out`` already
+    holds as copies: the chain's resident planes hold the fake run from here on."""
+    from . import fakes as fk
+    sci, ref, st = job.sci, job.ref, job.fake_settings
+    cat = out.get('cat')
+    if cat is None:                                    # the detection step failed on the real run: nothing to compare with
+        raise RuntimeError(f'no detection table of the real run: {out.get("detect_error")}')
+    good = cat[cat['GOODCUT'] == 1]
+    table = fk.draw_fakes(ch.shape, sci['wcs'], job.fakes['zp'], st,
+                          avoid_xy=(np.asarray(good['X_IMAGE'], np.float64) - 1.0, np.asarray(good['Y_IMAGE'], np.float64) - 1.0))
+    ckw = dict(wcs=sci['wcs'])
+    if getattr(job, 'rb_model', None) is not None:
+        # (the stamps' science plane is recover_dev's to name: its clone that holds the fakes)
+        ckw.update(rb_model=job.rb_model, ref=ref['img'], fid=job.fid, rb_cut=job.rb_cut,
+                   sci_flxscale=float(sci.get('flxscale', 1.0)))
+    for k in ('deblend', 'clean', 'mask'):
+        if getattr(job, k, None):
+            ckw[k] = getattr(job, k)
+    if getattr(job, 'columns', 'isophotal') != 'isophotal':
+        ckw['columns'] = job.columns
+    matched, _, _ = fk.recover_dev(ch, sci['img'], sci['rms'], sci['mask'], sci.get('wgt'), ref['img'], ref['rms'], ref['mask'],
+                                   float(sci['seeing']), table, job.fakes['psf'],
+                                   run_kws=dict(nreg_side=job.nreg_side, hotpants_kws=job.hotpants_kws,
+                                                ref_flxscale=float(ref.get('flxscale', 1.0))),
+                                   candidate_kws=ckw, gain=st['gain'], core_radius=st['core_radius'],
+                                   match_radius=st['match_radius'])
+    out['fakes'], out['efficiency'] = matched, fk.efficiency(matched)
 
 
 def _settle(out):
@@ -436,6 +503,8 @@ class SubtractionPool(object):
         if sync:
             torch.cuda.synchronize(self.device)           # inputs produced on other streams are complete
         jobs = list(jobs)
+        if self.batch and any(getattr(job, 'fakes', None) is not None for job in jobs):
+            raise ValueError('SubtractionJob(fakes=...) runs on the per-job workers: use SubtractionPool(njobs, batch=1)')
         if not self.batch:
             return list(self._pool.map(lambda j: self._run(j, keep), jobs))
         chunks = _batches([_fit_key(job) for job in jobs], self.batch)

@@ -2305,26 +2305,49 @@ __global__ __launch_bounds__(1024) void k_chol_back(int n, int lda, const double
 }
 
 // Back substitution for n <= CBC_COLS unknowns, one workgroup per region: thread 64 + c owns
-// column c and keeps y[c] in a register, wave 0 only runs the 32-step chain of each diagonal
-// block - beside the column sweep of the block solved before it (look-ahead, round 2: 72 -> 56 us).  The 32 rows of L a column thread needs for block kb - 1 are requested as soon as those
-// of block kb are consumed, and the diagonal block one step further ahead, so the chain of one
-// block covers the memory latency of the next: a step costs the chain plus two barriers
-// (k_chol_back above pays a dependent global load per block on top of it).
+// column c and keeps y[c] in a register, wave 0 runs the 32-step chain of each diagonal block.
+// The chain of block b needs, of the block b + 1 solved just before it, only the contribution to
+// its own 32 columns: wave 0 takes that one itself (the 32 x 32 block below the diagonal block is
+// staged in LDS beside the diagonal block, x of block b + 1 is still in its lanes), so between two
+// chains stands neither the column sweep nor a hand-over to it.  The column threads run one block
+// behind: while wave 0 solves block b they apply block b + 1 to the columns left of block b, hand
+// the sums of block b - 1's columns (every block but b applied, in descending order) to the chain,
+// and stage the blocks of chain b - 1, whose elements they requested one step earlier.  One barrier
+// per block instead of two; the rows of L are requested as the registers of the rows just consumed
+// fall free, a whole step before they are needed.  Every y[c] receives the same products in the
+// same order as before (one block of 32 at a time, m ascending; yc -= acc).
 #define CBC_THREADS 1024
 #define CBC_COLS (CBC_THREADS - 64)
+#define CBC_MAXBLK ((CBC_COLS + CH_NB - 1) / CH_NB)
+// Developer build: clocks per phase of workgroup 0 (wave 0 and the wave of columns 0 .. 63), summed over the blocks,
+// in cbc_clk; the shipped kernels carry none of it.
+#if ZM_DEV_BUILD
+__device__ long long cbc_clk[2][8];
+#define CBC_TICK(k) do { if (clk_on) { const long long t_ = __builtin_amdgcn_s_memtime(); ptk[k] += t_ - tc; tc = t_; } } while (0)
+#define CBC_ROWS_IN() __builtin_amdgcn_s_waitcnt(0x0F70)      /* vmcnt(0): the wait for the rows gets a phase of its own */
+#else
+#define CBC_TICK(k) do { } while (0)
+#define CBC_ROWS_IN() do { } while (0)
+#endif
 static __device__ __forceinline__ void chol_back_cols_body(int n, int lda, const double* __restrict__ Aall,
                                                                 const double* __restrict__ dall,
                                                                 double* __restrict__ xall, const int* __restrict__ guard) {
     if (guard && *guard == 0) return;                    // the previous round rejected nothing: this round is void
-    __shared__ double Dn[CH_NB][CH_NB + 1];      // diagonal block of the coming chain, 1 / diag in column 32
-    __shared__ double xs[2][CH_NB];              // the block just solved / the one being solved beside the sweep
-    __shared__ double ys[CH_NB];                 // right-hand side of the coming chain
+    // of the coming chain (slot b & 1 for block b: one is read by wave 0 while the other is filled):
+    __shared__ double Dn[2][CH_NB][CH_NB + 1];   // diagonal block: L[j][i] / L[j][j] below the diagonal, 0 on and above it, 1 / diag in column 32
+    __shared__ double Sn[2][CH_NB][CH_NB + 1];   // the block below it: Sn[m][i] = L[k0 + 32 + m][k0 + i], 0 in rows >= n
+    __shared__ double ys[2][CH_NB];              // right-hand side: the blocks above b + 1 applied (b + 1 is wave 0's)
+    __shared__ double xs[CBC_MAXBLK][CH_NB];     // every block solved so far
     const double* A = Aall + (size_t)blockIdx.x * (size_t)(n + 1) * lda;
     const int tid = threadIdx.x;
     const int nblk = (n + CH_NB - 1) / CH_NB;
+#if ZM_DEV_BUILD
+    const bool clk_on = blockIdx.x == 0 && (tid >> 6) < 2;
+    long long ptk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tc = clk_on ? __builtin_amdgcn_s_memtime() : 0;
+#endif
     // The two roles are two code paths with the same sequence of barriers (s_barrier counts waves, whatever their
-    // program counter): in one path the chain's 32 coefficients and the column threads' 32 rows of L were live
-    // together and the 128 registers of a wave (1024 threads) spilled.
+    // program counter), nblk + 1 of them: in one path the chain's 32 coefficients and the column threads' 32 rows of
+    // L were live together and the 128 registers of a wave (1024 threads) spilled.
     if (tid < 64) {
         // ---- wave 0: the 32-step chain of the block whose diagonal is in Dn and whose right-hand side is in ys.
         // Round 4: the chain carries the UNSCALED partial sums (the panel chains of the factorisation do the same):
@@ -2332,95 +2355,131 @@ static __device__ __forceinline__ void chol_back_cols_body(int n, int lda, const
         // rows j > i of its column and subtracts c[j] u_j as soon as u_j is final - a step is the broadcast of u_j
         // (v_readlane) and one FMA, the reciprocal diagonal comes in once at the end (before: two broadcasts, a
         // multiply, an FMA and two selects per step).  Dn holds 0 on and above the diagonal and the reciprocal
-        // diagonal in column 32: no select anywhere.
-        auto run_chain = [&](double* xout) {
-            const int li = tid & 31;
+        // diagonal in column 32: no select anywhere.  The products L[j][i] * (1 / L[j][j]) are formed by the
+        // threads that stage the block (same operands, same multiplication), not in front of every chain.
+        const int li = tid & 31;
+        double x = 0.0;                                      // lane m: x[m] of the block solved last
+        for (int b = nblk - 1; b >= 0; --b) {
+            __syncthreads();                                 // Dn, Sn, ys of block b are staged
+            CBC_TICK(0);
+            const int s = b & 1;
+            double u = ys[s][li];
+            if (b < nblk - 1) {
+                // block b + 1's contribution to the columns of block b, as a column thread forms it
+                double a[CH_NB];
+#pragma unroll
+                for (int m = 0; m < CH_NB; ++m) a[m] = Sn[s][m][li];
+                double acc = 0.0;
+#pragma unroll
+                for (int m = 0; m < CH_NB; ++m) acc += a[m] * readlane_d(x, m);
+                u -= acc;
+            }
+            CBC_TICK(1);
             double col[CH_NB];
 #pragma unroll
-            for (int j = 0; j < CH_NB; ++j) col[j] = Dn[j][li];
-            const double rdl = Dn[li][CH_NB];
-            double u = ys[li];
-#pragma unroll
-            for (int j = 1; j < CH_NB; ++j) col[j] *= readlane_d(rdl, j);
+            for (int j = 1; j < CH_NB; ++j) col[j] = Dn[s][j][li];
+            const double rdl = Dn[s][li][CH_NB];
 #pragma unroll
             for (int j = CH_NB - 1; j >= 1; --j) u = __builtin_fma(-col[j], readlane_d(u, j), u);
-            if (tid < CH_NB) xout[tid] = u * rdl;
-        };
-        __syncthreads();
-        run_chain(xs[0]);
-        __syncthreads();
-        for (int kb = nblk - 1; kb >= 1; --kb) {
-            __syncthreads();                                 // (phase A of the column threads)
-            run_chain(xs[(nblk - kb) & 1]);                  // block kb - 1, beside their phase B
-            __syncthreads();
+            x = u * rdl;
+            if (tid < CH_NB) xs[b][tid] = x;
+            CBC_TICK(2);
         }
+        __syncthreads();                                     // (x of block 0)
+#if ZM_DEV_BUILD
+        if (clk_on && tid == 0)
+            for (int k = 0; k < 8; ++k) cbc_clk[0][k] = ptk[k];
+#endif
         return;
     }
     const int c = tid - 64;
-    double yc = 0.0, a[CH_NB], dnext[2] = {0.0, 0.0};
-    // element e of a diagonal block (row e >> 5, column e & 31); rows >= nb are identity rows
-    auto diag_elem = [&](int k0, int nb, int e) -> double {
-        const int i = e >> 5, j = e & 31;
-        return (i < nb && j <= i) ? A[(size_t)(k0 + i) * lda + k0 + j] : (i == j ? 1.0 : 0.0);
+    const int B = nblk - 1;
+    double yc = 0.0, a[CH_NB];
+    // Staging for chain b: this thread carries the elements e = c and (the first 64 threads) c + CBC_COLS of its two
+    // 32 x 32 blocks, row i = e >> 5, column j = e & 31: sd = L[k0 + i][k0 + j] below the diagonal, sr the diagonal
+    // of that row (rows >= n are identity rows), ss = L[k0 + 32 + i][k0 + j] (0 in rows >= n: row n is the
+    // right-hand side).  Requested in one step, put into LDS in the next, read by wave 0 in the one after.
+    double sd[2] = {0.0, 0.0}, sr[2] = {1.0, 1.0}, ss[2] = {0.0, 0.0};
+    auto stage_load = [&](int b) {
+        const int k0 = b * CH_NB, nb = min(CH_NB, n - k0), k0u = k0 + CH_NB, nbu = min(CH_NB, n - k0u);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int e = c + q * CBC_COLS, i = e >> 5, j = e & 31;
+            if (q == 0 || e < CH_NB * CH_NB) {
+                sd[q] = (i < nb && j < i) ? A[(size_t)(k0 + i) * lda + k0 + j] : 0.0;
+                sr[q] = (i < nb) ? A[(size_t)(k0 + i) * lda + k0 + i] : 1.0;
+                ss[q] = (i < nbu) ? A[(size_t)(k0u + i) * lda + k0 + j] : 0.0;
+            }
+        }
     };
-    auto diag_put = [&](int e, double v) {
-        const int i = e >> 5, j = e & 31;
-        Dn[i][j] = (i == j) ? 0.0 : v;                   // (the chain wants the diagonal as its reciprocal only)
-        if (i == j) Dn[i][CH_NB] = 1.0 / v;
+    auto stage_put = [&](int b) {
+        const int s = b & 1;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int e = c + q * CBC_COLS, i = e >> 5, j = e & 31;
+            if (q == 0 || e < CH_NB * CH_NB) {
+                const double r = 1.0 / sr[q];                // (as many divisions side by side, none in the chain)
+                Dn[s][i][j] = sd[q] * r;
+                if (i == j) Dn[s][i][CH_NB] = r;
+                Sn[s][i][j] = ss[q];
+            }
+        }
     };
+    yc = (c < n) ? A[(size_t)n * lda + c] : 0.0;
+    stage_load(B);
+    stage_put(B);
+    if (c >= B * CH_NB && c < nblk * CH_NB) ys[B & 1][c - B * CH_NB] = yc;       // 0 beyond column n - 1
+    if (B >= 1) stage_load(B - 1);
     {
-        const int kb = nblk - 1, k0 = kb * CH_NB, nb = n - k0;
-        yc = (c < n) ? A[(size_t)n * lda + c] : 0.0;
-        diag_put(c, diag_elem(k0, nb, c));
-        if (c + CBC_COLS < CH_NB * CH_NB) diag_put(c + CBC_COLS, diag_elem(k0, nb, c + CBC_COLS));
-        if (c >= k0 && c < k0 + CH_NB) ys[c - k0] = yc;          // 0 beyond column n - 1
+        // the rows of block B for the columns left of block B - 1 (wave 0 applies block B to block B - 1's)
+        const int k0 = B * CH_NB, nb = n - k0, lim = k0 - CH_NB;
 #pragma unroll
-        for (int m = 0; m < CH_NB; ++m) a[m] = (c < k0 && m < nb) ? A[(size_t)(k0 + m) * lda + c] : 0.0;
-        if (kb > 0) {
-            dnext[0] = diag_elem(k0 - CH_NB, CH_NB, c);
-            if (c + CBC_COLS < CH_NB * CH_NB) dnext[1] = diag_elem(k0 - CH_NB, CH_NB, c + CBC_COLS);
+        for (int m = 0; m < CH_NB; ++m) a[m] = 0.0;
+        if (c < lim) {
+#pragma unroll
+            for (int m = 0; m < CH_NB; ++m)
+                if (m < nb) a[m] = A[(size_t)(k0 + m) * lda + c];
         }
     }
-    __syncthreads();
-    // Look-ahead: once block kb is solved, the 32 columns of block kb - 1 take its contribution first
-    // (phase A), then wave 0 runs the chain of block kb - 1 WHILE the other columns take theirs and
-    // request the rows of the next block (phase B) - the chain overlaps the column sweep and its
-    // loads instead of standing between them.  Every y[c] still receives the same products in the
-    // same order (one block of 32 at a time, m ascending).
-    __syncthreads();                                         // (the chain of the last block)
-    for (int kb = nblk - 1; kb >= 1; --kb) {
-        const int k0 = kb * CH_NB, nb = min(CH_NB, n - k0);
-        const int k0n = k0 - CH_NB;
-        const double* xc = xs[(nblk - 1 - kb) & 1];          // solution of block kb
-        // ---- phase A: this block's columns are final; the next block's columns finish their sums
-        if (c >= k0 && c < k0 + nb) yc = xc[c - k0];
-        if (c >= k0n && c < k0) {
+    CBC_TICK(0);
+    __syncthreads();                                         // chain B is staged
+    for (int b = B; b >= 0; --b) {
+        // ---- beside the chain of block b
+        CBC_TICK(1);
+        if (b >= 1) stage_put(b - 1);                        // (requested a step ago)
+        if (b >= 2) stage_load(b - 2);
+        CBC_TICK(2);
+        if (b < B && c < b * CH_NB) {
+            // block b + 1 to the columns left of block b, and the rows of block b for those left of block b - 1
+            const double* xc = xs[b + 1];
+            const int k0 = b * CH_NB, lim = k0 - CH_NB;
+            CBC_ROWS_IN();
+            CBC_TICK(3);
             double acc = 0.0;
+            if (c < lim) {
+                // (each row is requested as the register of the row just consumed falls free)
+                const double* ap = A + (size_t)k0 * lda + c;
 #pragma unroll
-            for (int m = 0; m < CH_NB; ++m) acc += a[m] * xc[m];
+                for (int m = 0; m < CH_NB; ++m) {
+                    acc += a[m] * xc[m];
+                    a[m] = ap[(size_t)m * lda];
+                }
+            } else {                                         // the columns of block b - 1: wave 0 takes block b to them
+#pragma unroll
+                for (int m = 0; m < CH_NB; ++m) acc += a[m] * xc[m];
+            }
             yc -= acc;
-            ys[c - k0n] = yc;
         }
-        diag_put(c, dnext[0]);
-        if (c + CBC_COLS < CH_NB * CH_NB) diag_put(c + CBC_COLS, dnext[1]);
-        __syncthreads();
-        // ---- phase B: the sweep of the columns left of block kb - 1, beside its chain
-        if (c < k0n) {
-            double acc = 0.0;
-#pragma unroll
-            for (int m = 0; m < CH_NB; ++m) acc += a[m] * xc[m];
-            yc -= acc;
-        }
-#pragma unroll
-        for (int m = 0; m < CH_NB; ++m) a[m] = (c < k0n) ? A[(size_t)(k0n + m) * lda + c] : 0.0;
-        if (kb > 1) {
-            dnext[0] = diag_elem(k0n - CH_NB, CH_NB, c);
-            if (c + CBC_COLS < CH_NB * CH_NB) dnext[1] = diag_elem(k0n - CH_NB, CH_NB, c + CBC_COLS);
-        }
-        __syncthreads();
+        if (b >= 1 && c >= (b - 1) * CH_NB && c < b * CH_NB) ys[(b - 1) & 1][c - (b - 1) * CH_NB] = yc;
+        CBC_TICK(4);
+        __syncthreads();                                     // chain b - 1 is staged, x of block b is out
     }
-    if (c < min(CH_NB, n)) yc = xs[(nblk - 1) & 1][c];       // block 0
-    if (c < n) xall[(size_t)blockIdx.x * n + c] = yc / dall[(size_t)blockIdx.x * n + c];
+    CBC_TICK(1);
+    if (c < n) xall[(size_t)blockIdx.x * n + c] = xs[c >> 5][c & 31] / dall[(size_t)blockIdx.x * n + c];
+#if ZM_DEV_BUILD
+    if (clk_on && c == 0)
+        for (int k = 0; k < 8; ++k) cbc_clk[1][k] = ptk[k];
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -3472,6 +3531,19 @@ extern "C" int zm_subtract_dev(zm_ctx* ctx, const float* sci, const float* sci_r
                     hipLaunchKernelGGL(k_chol_back_cols, dim3(P.nreg), dim3(CBC_THREADS), 0, st, P.nunk, lda, A, dsc, rhs, guard);
                 else
                     hipLaunchKernelGGL(k_chol_back, dim3(P.nreg), dim3(1024), bsh, st, P.nunk, lda, A, dsc, rhs, guard);
+#if ZM_DEV_BUILD
+                // ZM_CBC_PROF=1: the phase clocks of region 0's back substitution, per launch (100 MHz ticks)
+                if (P.nunk <= CBC_COLS && ZM_DEVENV("ZM_CBC_PROF")) {
+                    long long ck[2][8];
+                    ZM_HIP(hipStreamSynchronize(st));
+                    ZM_HIP(hipMemcpyFromSymbol(ck, HIP_SYMBOL(cbc_clk), sizeof(ck)));
+                    const int nb_ = (P.nunk + CH_NB - 1) / CH_NB;
+                    fprintf(stderr, "back_cols n %d blocks %d, us per block: chain wave: barrier %.3f  block above %.3f  chain %.3f | "
+                            "column wave 1: barrier %.3f  staging %.3f  rows %.3f  sweep %.3f | prologue %.2f us\n", P.nunk, nb_,
+                            ck[0][0] * 0.01 / nb_, ck[0][1] * 0.01 / nb_, ck[0][2] * 0.01 / nb_, ck[1][1] * 0.01 / nb_,
+                            ck[1][2] * 0.01 / nb_, ck[1][3] * 0.01 / nb_, ck[1][4] * 0.01 / nb_, ck[1][0] * 0.01);
+                }
+#endif
             }
             hipLaunchKernelGGL(k_hp_merit, dim3(P.ncell), dim3(64), 0, st, P, G, phi, vbar, active, rhs, merit, guard, needlist);
             const hp_sig sig = sig_off ? hp_sig{nullptr, nullptr, 0u} : hp_sig{rflags + 16 + rounds, ctx->hp_sig_d + rounds, seq};

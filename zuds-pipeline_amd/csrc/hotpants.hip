@@ -3300,7 +3300,9 @@ extern "C" int zm_subtract_dev(zm_ctx* ctx, const float* sci, const float* sci_r
     ZM_TRY(hp_launch_cells(ctx, P, ref, bad, dirty, centres, active, need, ntotal));
     // LDS of k_hp_vectors
     const hv_cfg hvc = hp_vectors_cfg(P.pw, P.sw, P.npix);
-    ZM_CHECK(hvc.cw >= 8, "zm_subtract: r = %d, rss = %d: the template patch alone exceeds the LDS", P.hwk, P.hwss);
+    // (the chunked form needs a chunk of at least HV_R columns; the resident form holds all sw columns, also the
+    // 3, 5 or 7 of a substamp half width below 4)
+    ZM_CHECK(!hvc.big || hvc.cw >= 8, "zm_subtract: r = %d, rss = %d: the template patch alone exceeds the LDS", P.hwk, P.hwss);
     size_t vsh = hvc.shmem;
     // (the chunked form: term 0 of every workgroup of the launch in global memory; the grid is capped, cells loop)
     const int hv_gx = hvc.big ? std::min(P.ncell, 128) : P.ncell;

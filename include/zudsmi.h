@@ -1181,11 +1181,32 @@ int zm_astrom_solve(zm_ctx* ctx, int nframes, const zm_wcs* wcs0, const int32_t*
 /* ---- FITS data blocks on the device ------------------------------------------ */
 /* Replaces the host-side decode / encode astropy does inside FITSFile.load_data / save
  * (zuds/fitsfile.py:69-94,146-206): raw_dev holds the big-endian data block of a primary
- * HDU as it lies on disk (n pixels of BITPIX 8 / 16 / 32 / -32 / -64); the decoded plane
- * is float32 (out_kind 0), int32 (1), uint8 (2) or int16 (3: a BITPIX 16 mask kept at 16 bits for
- * zm_dframe.mask_type = ZM_MASKTYPE_I16) with physical = bzero + bscale * stored.
+ * HDU as it lies on disk (n pixels of BITPIX 8 / 16 / 32 / 64 / -32 / -64; stored values are
+ * uint8, int16, int32, int64, float32, float64); the decoded plane is float32 (out_kind 0), int32 (1),
+ * uint8 (2) or int16 (3: a BITPIX 16 mask kept at 16 bits for zm_dframe.mask_type = ZM_MASKTYPE_I16)
+ * with physical = bzero + bscale * stored.  "Unscaled" below: bscale == 1 and bzero == 0.
+ *
+ * The contract (restated by tests/fits_ref.py, pinned by tests/test_fits_decode_gpu.py):
+ *  - float32 out, unscaled BITPIX -32: the 32 bits of the file, byte-swapped.  NaN payload and
+ *    sign, -0.0 and subnormals are unchanged.
+ *  - float32 out, unscaled integer BITPIX (64 included): the integer converted directly, one
+ *    rounding to nearest even, never through fp64 (numpy's int64 -> float32).
+ *  - float32 out, anything else: fl(stored) * bscale rounded to fp64, + bzero rounded to fp64,
+ *    rounded once to float32; two fp64 operations, never a fused multiply-add.  (fl(stored) is
+ *    exact but for BITPIX 64 beyond 2^53.)  Bit for bit what fits.read(...) followed by
+ *    .astype(float32) gives; the one exception is BITPIX 64 with BSCALE 1 and an integer BZERO,
+ *    where the host reader adds in int64 and rounds once.  A NaN that comes out of the
+ *    arithmetic or out of float64 -> float32 is a NaN of no particular payload.
+ *  - int32 / uint8 / int16 out: the same fp64 value, truncated toward zero and SATURATED at the
+ *    ends of the output type (+-inf included); NaN gives 0.  Unscaled integer blocks, and
+ *    BSCALE 1 with an integer BZERO of magnitude <= 2^63 (the unsigned 16 / 32 / 64 bit and
+ *    signed-byte conventions), stay in exact integer arithmetic - stored + BZERO without
+ *    rounding, also where that sum leaves int64 - and saturate in the same way: an unsigned-16
+ *    file read as int16 gives 32767 for 40000, not -25536.
+ *  - BLANK is not implemented (nor is it by the host reader).
  * Encode: float32 -> BITPIX -32 (in_kind 0), int32 -> 32 (1), uint8 -> 8 (2),
- * int32 -> BITPIX 16 (3). */
+ * int32 -> BITPIX 16 (3): the bits of the plane, byte-swapped; in_kind 3 writes the low 16 bits,
+ * so values must lie within -32768 .. 32767 (the caller's duty). */
 int zm_fits_decode_dev(zm_ctx* ctx, const void* raw_dev, int bitpix, double bscale,
                        double bzero, int64_t n, int out_kind, void* out_dev);
 int zm_fits_encode_dev(zm_ctx* ctx, const void* in_dev, int in_kind, int64_t n,
